@@ -8,6 +8,9 @@ trials. The Parzen KDE fit (K1) and the S×K×D mixture log-pdf / EI scoring (K2
 run as hand-written HIP kernels on gfx950.
 
 Single process: `python bench.py --steps 64 --warmup 8`
+  A plain run sets up, warms up, times `--steps` steps and prints one JSON result
+  line. `--dump-outputs DIR` also writes what the last timed step returned;
+  `--full` is where any measurement beyond the headline figure belongs.
 Multi GPU (driver): torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
   → one worker process per GPU, all sharing one study through the distributed
     op-log storage (RcclStorage) — weak scaling (K steps per rank).
@@ -40,6 +43,21 @@ def main() -> None:
         choices=("tpe", "random", "gp", "cmaes", "cmaes_hb", "nsgaii", "motpe", "motpe3"),
         default="tpe",
         help="BASELINE.json config to run (default: the headline TPE config)",
+    )
+    parser.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write the last timed step's suggested "
+        "parameters and objective values to DIR/params.npy and DIR/values.npy "
+        "(float64)",
+    )
+    parser.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the measurements and checks that go beyond the headline "
+        "figure (none at present: a plain run already does only setup, warmup "
+        "and the timed steps)",
     )
     args = parser.parse_args()
 
@@ -220,6 +238,9 @@ def main() -> None:
 
     if rank == 0:
         from optuna_amd import _hip
+
+        if args.dump_outputs and args.steps > 0:
+            _dump_outputs(args.dump_outputs, study)
 
         value = n_gpus * args.steps / elapsed
         if cmaes_hb:
@@ -446,6 +467,9 @@ def _run_alt_suite(args: argparse.Namespace) -> None:
         one_step()
     elapsed = time.perf_counter() - t0
 
+    if args.dump_outputs and args.steps > 0:
+        _dump_outputs(args.dump_outputs, study)
+
     print(
         json.dumps(
             {
@@ -466,6 +490,26 @@ def _run_alt_suite(args: argparse.Namespace) -> None:
         ),
         flush=True,
     )
+
+
+def _dump_outputs(out_dir: str, study) -> None:
+    """Write what the last timed step handed back to its caller.
+
+    ``params.npy`` holds the suggested parameter values in suggestion order and
+    ``values.npy`` the objective values told for that trial (NaN where the trial
+    was pruned), both float64. Seeds are fixed, so equal arguments give equal
+    inputs from run to run.
+    """
+    trial = study.get_trials(deepcopy=False)[-1]
+    params = np.asarray(list(trial.params.values()), dtype=np.float64)
+    if trial.values is None:
+        values = np.full(len(study.directions), np.nan, dtype=np.float64)
+    else:
+        values = np.asarray(trial.values, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "params.npy"), params)
+    np.save(os.path.join(out_dir, "values.npy"), values)
+    _log(f"wrote params.npy {params.shape} and values.npy {values.shape} to {out_dir}")
 
 
 def _populate(study, names, dists_def, n_history: int) -> None:

@@ -61,25 +61,48 @@ def test_wire_proxy_end_to_end(wire_pair) -> None:
 
 
 def test_reference_stub_against_our_server(wire_pair) -> None:
-    """The reference's generated protobuf classes drive our wire server."""
-    import importlib.util
-    import os
-    import sys
+    """The reference's generated protobuf classes drive our wire server.
 
-    path = "/root/reference/optuna/storages/_grpc/auto_generated"
-    if not os.path.isdir(path):
-        pytest.skip("reference checkout not available")
-    spec = importlib.util.spec_from_file_location("api_pb2", f"{path}/api_pb2.py")
-    pb2 = importlib.util.module_from_spec(spec)
-    sys.modules["api_pb2"] = pb2
-    try:
-        spec.loader.exec_module(pb2)
-    except Exception as e:
-        pytest.skip(f"reference pb2 not loadable: {e}")
+    Always replayed from the request bytes those classes emitted when
+    ``tests/golden/reference/grpc_wire.json`` was recorded; with a reference
+    checkout at hand (OPTUNA_REFERENCE_PATH) its classes also drive the server
+    live."""
     import grpc
 
-    client, _ = wire_pair
+    from test_grpc_wire import GOLDEN, _load_ref_pb2
+
+    from optuna_amd.storages._grpc import _wire
+
+    client, backend = wire_pair
     channel = grpc.insecure_channel(f"127.0.0.1:{client._port}")
+
+    # The recorded requests name study 2 and trial 3: occupy the ids before them.
+    for i in range(2):
+        filler = backend.create_new_study([optuna_amd.study.StudyDirection.MINIMIZE], f"f{i}")
+    for _ in range(3):
+        backend.create_new_trial(filler)
+
+    def raw_call(method: str) -> dict:
+        call = channel.unary_unary(
+            f"/optuna.StorageService/{method}",
+            request_serializer=lambda b: b,
+            response_deserializer=lambda b: b,
+        )
+        reply = call(bytes.fromhex(GOLDEN["stub_requests"][method]))
+        return _wire.decode(_wire.METHODS[method][1], reply)
+
+    assert raw_call("CreateNewStudy")["study_id"] == 2
+    assert client.get_study_id_from_name("refstub") == 2
+    assert raw_call("CreateNewTrial")["trial_id"] == 3
+    replayed = raw_call("GetTrial")["trial"]
+    assert replayed["trial_id"] == 3 and replayed["state"] == GOLDEN["enums"]["RUNNING"]
+    assert client.get_trial(3).state == TrialState.RUNNING
+    backend.delete_study(2)
+
+    pb2 = _load_ref_pb2()
+    if pb2 is None:
+        channel.close()
+        return
     call = channel.unary_unary(
         "/optuna.StorageService/CreateNewStudy",
         request_serializer=lambda m: m.SerializeToString(),

@@ -89,6 +89,10 @@ def _worker(rank: int, world_size: int, port: int, queue) -> None:
 
         while store.add("done", 0) < world_size:
             time.sleep(0.01)
+        # Reads are rate-limited and may serve a view up to 25 sync TTLs old;
+        # the other worker's last tell can be younger than that, so pull the
+        # log's tail before counting.
+        storage._sync(force=True)
         trials = study.get_trials(deepcopy=False)
         queue.put((rank, len(trials), [t.number for t in trials]))
         # The rank-0 process hosts the TCPStore: keep it alive until every

@@ -265,14 +265,66 @@ def test_reference_reads_our_upgraded_db(tmp_path) -> None:
     import os
     import sys
     import types
+    from pathlib import Path
 
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference tree not available")
     db = str(tmp_path / "up.db")
     _make_v09_db(db)
     url = f"sqlite:///{db}"
     storage = RDBStorage(url, skip_compatibility_check=True)
     storage.upgrade()
+
+    # First through the reference's table layout and stored representations as
+    # recorded in tests/golden/reference/rdb_models.json: runs anywhere.
+    golden = json.loads(
+        (Path(__file__).parent / "golden" / "reference" / "rdb_models.json").read_text()
+    )
+    ref_tables = golden["tables"]
+    conn = sqlite3.connect(db)
+    cur = conn.cursor()
+    for table, ref_cols in ref_tables.items():
+        cur.execute(f"PRAGMA table_info({table})")
+        info = {row[1]: row for row in cur.fetchall()}
+        assert set(info) == set(ref_cols), f"column mismatch in {table}"
+        for col_name, ref_col in ref_cols.items():
+            assert bool(info[col_name][5]) == ref_col["primary_key"], (table, col_name)
+            if ref_col["enums"] is not None:
+                cur.execute(f"SELECT DISTINCT {col_name} FROM {table}")
+                stored = {row[0] for row in cur.fetchall()}
+                assert stored <= set(ref_col["enums"]), (table, col_name, stored)
+    cur.execute("SELECT trial_id, number FROM trials ORDER BY number")
+    trial_rows = cur.fetchall()
+    assert [number for _, number in trial_rows] == [0, 1, 2, 3]
+    trial_ids = [trial_id for trial_id, _ in trial_rows]
+    cur.execute("SELECT trial_id, value, value_type FROM trial_values")
+    stored_values = {trial_id: (value, vtype) for trial_id, value, vtype in cur.fetchall()}
+    assert stored_values[trial_ids[0]] == (1.5, "FINITE")
+    assert stored_values[trial_ids[1]][1] == "INF_POS"
+    assert trial_ids[2] not in stored_values  # PRUNED without value
+    cur.execute(
+        "SELECT param_name, distribution_json FROM trial_params WHERE trial_id = ?",
+        (trial_ids[0],),
+    )
+    param_rows = cur.fetchall()
+    assert {name for name, _ in param_rows} == {"x", "n"}
+    for _, distribution_json in param_rows:
+        assert "Distribution" in distribution_json  # new-format JSON
+        assert "Uniform" not in distribution_json
+    cur.execute(
+        "SELECT intermediate_value, intermediate_value_type FROM trial_intermediate_values"
+        " WHERE trial_id = ? AND step = 0",
+        (trial_ids[0],),
+    )
+    assert cur.fetchall() == [(0.5, "FINITE")]
+    cur.execute("SELECT direction FROM study_directions")
+    assert [row[0] for row in cur.fetchall()] == ["MINIMIZE"]
+    cur.execute("SELECT schema_version FROM version_info")
+    assert cur.fetchall() == [(golden["schema_version"],)]
+    conn.close()
+
+    # Then, where OPTUNA_REFERENCE_PATH names a checkout, through the live library.
+    reference_path = os.environ.get("OPTUNA_REFERENCE_PATH")
+    if not reference_path or not os.path.isdir(reference_path):
+        return
 
     if "colorlog" not in sys.modules:  # the reference hard-requires colorlog
         stub = types.ModuleType("colorlog")
@@ -287,9 +339,9 @@ def test_reference_reads_our_upgraded_db(tmp_path) -> None:
         stub.TTYColoredFormatter = _Fmt
         stub.StreamHandler = _logging.StreamHandler
         sys.modules["colorlog"] = stub
-    if "/root/reference" not in sys.path:
-        sys.path.insert(0, "/root/reference")
-    # alembic is not installed here and the reference's RDBStorage imports it;
+    if reference_path not in sys.path:
+        sys.path.insert(0, reference_path)
+    # the reference's RDBStorage imports alembic, which may not be installed;
     # read the upgraded file through the reference's ORM MODELS instead — the
     # schema contract is what the upgrade must satisfy.
     import sqlalchemy as sa

@@ -1,27 +1,37 @@
 """Checkpoint-format interop with the reference implementation.
 
-These tests import the read-only reference library (mounted at /root/reference)
-and verify that studies written by optuna_amd through the RDB (schema v12) and
-journal backends load back identically through the reference, and vice versa.
-Skipped automatically when the reference tree is unavailable.
+These tests verify that studies written by optuna_amd through the RDB (schema
+v12) and journal backends are what the reference writes and reads, and vice
+versa. The reference's side is replayed from ``tests/golden/reference/``
+(its ORM table layout, its distribution JSON and a journal log it wrote, all
+recorded by ``scripts/record_reference_goldens.py``), so the tests run
+anywhere. Where OPTUNA_REFERENCE_PATH names a reference checkout they also
+exercise it live.
 """
 from __future__ import annotations
 
+import json
+import os
+import shutil
 import sys
 import types
+from pathlib import Path
 
 import pytest
 
 
-REFERENCE_PATH = "/root/reference"
+GOLDEN_DIR = Path(__file__).parent / "golden" / "reference"
+GOLDEN_MODELS = json.loads((GOLDEN_DIR / "rdb_models.json").read_text())
+GOLDEN_JOURNAL = GOLDEN_DIR / "journal_interop.log"
 
 
 @pytest.fixture(scope="module")
 def reference_optuna():
-    import os
-
-    if not os.path.isdir(REFERENCE_PATH):
-        pytest.skip("reference tree not available")
+    """The live reference library, or None where no checkout is configured."""
+    reference_path = os.environ.get("OPTUNA_REFERENCE_PATH")
+    if not reference_path or not os.path.isdir(reference_path):
+        yield None
+        return
     # The reference hard-requires colorlog; provide a minimal stand-in.
     if "colorlog" not in sys.modules:
         import logging as _logging
@@ -42,13 +52,13 @@ def reference_optuna():
         stub.TTYColoredFormatter = _TTYFmt  # type: ignore[attr-defined]
         stub.StreamHandler = _logging.StreamHandler  # type: ignore[attr-defined]
         sys.modules["colorlog"] = stub
-    sys.path.insert(0, REFERENCE_PATH)
+    sys.path.insert(0, reference_path)
     try:
         import optuna as reference
 
         yield reference
     finally:
-        sys.path.remove(REFERENCE_PATH)
+        sys.path.remove(reference_path)
 
 
 def _populate(module, storage_url: str) -> None:
@@ -90,42 +100,54 @@ def _check(module, storage_url: str) -> None:
     assert best.value == max(t.value for t in trials)
 
 
+def _describe_tables(models) -> dict:  # type: ignore[no-untyped-def]
+    """Table layout of an ORM models module, in the recorded fixture's form."""
+    return {
+        name: {
+            c.name: {
+                "primary_key": bool(c.primary_key),
+                "type": type(c.type).__name__,
+                "enums": list(c.type.enums) if hasattr(c.type, "enums") else None,
+            }
+            for c in table.columns
+        }
+        for name, table in models.BaseModel.metadata.tables.items()
+    }
+
+
 def test_rdb_schema_matches_reference_models(reference_optuna) -> None:
     """Table/column/type-level comparison against the reference ORM metadata.
 
-    (The reference's RDBStorage itself needs alembic, unavailable here; its
-    models module imports cleanly and defines the authoritative schema.)
+    (The reference's RDBStorage itself needs alembic; its models module imports
+    cleanly and defines the authoritative schema.)
     """
-    import importlib
-
-    ref_models = importlib.import_module("optuna.storages._rdb.models")
     import optuna_amd.storages._rdb.models as our_models
 
-    assert our_models.SCHEMA_VERSION == ref_models.SCHEMA_VERSION == 12
+    ref_tables = GOLDEN_MODELS["tables"]
+    if reference_optuna is not None:
+        import importlib
 
-    ref_tables = ref_models.BaseModel.metadata.tables
-    our_tables = our_models.BaseModel.metadata.tables
+        ref_models = importlib.import_module("optuna.storages._rdb.models")
+        # The recorded layout is the live reference's.
+        assert _describe_tables(ref_models) == ref_tables
+        assert ref_models.SCHEMA_VERSION == GOLDEN_MODELS["schema_version"]
+
+    assert our_models.SCHEMA_VERSION == GOLDEN_MODELS["schema_version"] == 12
+
+    our_tables = _describe_tables(our_models)
     assert set(our_tables) == set(ref_tables)
 
     for name in sorted(ref_tables):
-        ref_cols = {c.name: c for c in ref_tables[name].columns}
-        our_cols = {c.name: c for c in our_tables[name].columns}
+        ref_cols = ref_tables[name]
+        our_cols = our_tables[name]
         assert set(our_cols) == set(ref_cols), f"column mismatch in {name}"
         for col_name, ref_col in ref_cols.items():
             our_col = our_cols[col_name]
-            assert our_col.primary_key == ref_col.primary_key, (name, col_name)
-            assert type(our_col.type).__name__ == type(ref_col.type).__name__, (
-                name,
-                col_name,
-                our_col.type,
-                ref_col.type,
-            )
+            assert our_col["primary_key"] == ref_col["primary_key"], (name, col_name)
+            assert our_col["type"] == ref_col["type"], (name, col_name)
             # Enum columns must serialize the same labels.
-            if hasattr(ref_col.type, "enums"):
-                assert list(our_col.type.enums) == list(ref_col.type.enums), (
-                    name,
-                    col_name,
-                )
+            if ref_col["enums"] is not None:
+                assert our_col["enums"] == ref_col["enums"], (name, col_name)
 
 
 def test_sqlite_roundtrip_through_raw_schema(reference_optuna, tmp_path) -> None:
@@ -150,12 +172,48 @@ def test_sqlite_roundtrip_through_raw_schema(reference_optuna, tmp_path) -> None
     )
     rows = {name: (value, dist_json) for name, value, dist_json in cur.fetchall()}
     assert set(rows) == {"x", "lg", "i", "c"}
-    # distribution_json decodes through the REFERENCE codec.
-    ref_dist = reference_optuna.distributions.json_to_distribution(rows["x"][1])
-    assert ref_dist.low == -5.0 and ref_dist.high == 5.0
+    # distribution_json says what the REFERENCE codec writes for this distribution.
+    assert json.loads(rows["x"][1]) == json.loads(GOLDEN_MODELS["float_distribution_json"])
+    if reference_optuna is not None:
+        # ... and decodes through it.
+        ref_dist = reference_optuna.distributions.json_to_distribution(rows["x"][1])
+        assert ref_dist.low == -5.0 and ref_dist.high == 5.0
     cur.execute("SELECT value_type FROM trial_values LIMIT 1")
     assert cur.fetchone()[0] == "FINITE"
     conn.close()
+
+
+# Per-run fields (who wrote the op, when) and what the sampler drew.
+_VOLATILE_OP_KEYS = (
+    "worker_id",
+    "datetime_start",
+    "datetime_complete",
+    "param_value_internal",
+    "intermediate_value",
+    "values",
+)
+
+
+def _type_names(value):  # type: ignore[no-untyped-def]
+    if isinstance(value, list):
+        return [_type_names(v) for v in value]
+    return type(value).__name__
+
+
+def _journal_ops(path) -> list:  # type: ignore[no-untyped-def]
+    """A journal log's ops with the per-run fields reduced to their JSON types
+    and the embedded distribution JSON parsed (its key order is not significant)."""
+    ops = []
+    with open(path) as f:
+        for line in f:
+            op = json.loads(line)
+            for key in _VOLATILE_OP_KEYS:
+                if key in op:
+                    op[key] = _type_names(op[key])
+            if "distribution" in op:
+                op["distribution"] = json.loads(op["distribution"])
+            ops.append(op)
+    return ops
 
 
 def test_reference_reads_our_journal(reference_optuna, tmp_path) -> None:
@@ -167,22 +225,35 @@ def test_reference_reads_our_journal(reference_optuna, tmp_path) -> None:
     )
     _populate(optuna_amd, storage)
 
-    ref_storage = reference_optuna.storages.JournalStorage(
-        reference_optuna.storages.journal.JournalFileBackend(path)
-    )
-    _check(reference_optuna, ref_storage)
+    # Op for op, our log is the one the reference wrote for the same study.
+    assert _journal_ops(path) == _journal_ops(GOLDEN_JOURNAL)
+
+    if reference_optuna is not None:
+        ref_storage = reference_optuna.storages.JournalStorage(
+            reference_optuna.storages.journal.JournalFileBackend(path)
+        )
+        _check(reference_optuna, ref_storage)
 
 
 def test_we_read_reference_journal(reference_optuna, tmp_path) -> None:
     import optuna_amd
 
-    path = str(tmp_path / "theirs.log")
-    ref_storage = reference_optuna.storages.JournalStorage(
-        reference_optuna.storages.journal.JournalFileBackend(path)
-    )
-    _populate(reference_optuna, ref_storage)
-
+    # The log the reference wrote when the fixture was recorded.
+    path = str(tmp_path / "recorded.log")
+    shutil.copyfile(GOLDEN_JOURNAL, path)
     storage = optuna_amd.storages.JournalStorage(
         optuna_amd.storages.JournalFileBackend(path)
     )
     _check(optuna_amd, storage)
+
+    if reference_optuna is not None:
+        path = str(tmp_path / "theirs.log")
+        ref_storage = reference_optuna.storages.JournalStorage(
+            reference_optuna.storages.journal.JournalFileBackend(path)
+        )
+        _populate(reference_optuna, ref_storage)
+
+        storage = optuna_amd.storages.JournalStorage(
+            optuna_amd.storages.JournalFileBackend(path)
+        )
+        _check(optuna_amd, storage)
