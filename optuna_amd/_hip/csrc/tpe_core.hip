@@ -217,7 +217,8 @@ __global__ void k_mix_logpdf(const double* __restrict__ x,  // (S, D)
     }
     __syncthreads();
 
-    // Online logsumexp per thread.
+    // Online logsumexp per thread. While m is still -inf a term t == -inf
+    // (zero mixture weight) adds nothing; exp(t - m) would be exp(NaN).
     double m = -INFINITY, acc = 0.0;
     for (int64_t k = threadIdx.x; k < K; k += blockDim.x) {
         double t = logw[k];
@@ -228,7 +229,7 @@ __global__ void k_mix_logpdf(const double* __restrict__ x,  // (S, D)
         if (t > m) {
             acc = acc * exp(m - t) + 1.0;
             m = t;
-        } else {
+        } else if (m != -INFINITY) {
             acc += exp(t - m);
         }
     }
@@ -316,7 +317,7 @@ __global__ void k_mix_logpdf_partial(const double* __restrict__ x,  // (S, D)
             if (t > m) {
                 acc = acc * exp(m - t) + 1.0;
                 m = t;
-            } else {
+            } else if (m != -INFINITY) {
                 acc += exp(t - m);
             }
         }
@@ -330,7 +331,7 @@ __global__ void k_mix_logpdf_partial(const double* __restrict__ x,  // (S, D)
             if (t > m) {
                 acc = acc * exp(m - t) + 1.0;
                 m = t;
-            } else {
+            } else if (m != -INFINITY) {
                 acc += exp(t - m);
             }
         }
@@ -440,7 +441,7 @@ __global__ void k_mix_logpdf_perdim(const double* __restrict__ x,  // (S, D)
         if (t > m) {
             acc = acc * exp(m - t) + 1.0;
             m = t;
-        } else {
+        } else if (m != -INFINITY) {
             acc += exp(t - m);
         }
     }

@@ -1,6 +1,9 @@
 """Golden tests: host truncnorm vs scipy.stats.truncnorm (and later the HIP K3 lib)."""
 from __future__ import annotations
 
+import json
+from pathlib import Path
+
 import numpy as np
 import pytest
 from scipy import stats
@@ -64,3 +67,50 @@ def test_rvs_seeded_within_bounds() -> None:
     rng2 = np.random.RandomState(0)
     draws2 = tn.rvs(a, b, loc=1.0, scale=0.5, random_state=rng2)
     np.testing.assert_array_equal(draws, draws2)
+
+
+# ---- mpmath golden points (tests/golden/truncnorm_edges.json) -----------------------
+
+_GOLDEN_PATH = Path(__file__).resolve().parent.parent / "golden" / "truncnorm_edges.json"
+_GOLDEN = json.loads(_GOLDEN_PATH.read_text())
+
+
+def _col(section: str, key: str) -> np.ndarray:
+    return np.array([p[key] for p in _GOLDEN[section]], dtype=np.float64)
+
+
+def test_log_gauss_mass_matches_mpmath_golden() -> None:
+    with np.errstate(all="ignore"):
+        ours = tn._log_gauss_mass(_col("log_gauss_mass", "a"), _col("log_gauss_mass", "b"))
+    np.testing.assert_allclose(ours, _col("log_gauss_mass", "expected"), rtol=1e-10, atol=1e-12)
+
+
+def test_ppf_matches_mpmath_golden() -> None:
+    with np.errstate(all="ignore"):
+        ours = tn.ppf(_col("ppf", "q"), _col("ppf", "a"), _col("ppf", "b"))
+    np.testing.assert_allclose(ours, _col("ppf", "expected"), rtol=1e-8, atol=1e-10)
+
+
+def test_logpdf_matches_mpmath_golden() -> None:
+    with np.errstate(all="ignore"):
+        ours = tn.logpdf(
+            _col("logpdf", "x"), _col("logpdf", "a"), _col("logpdf", "b"),
+            _col("logpdf", "loc"), _col("logpdf", "scale"),
+        )
+    expected = _col("logpdf", "expected")
+    assert np.isneginf(expected).sum() >= 10  # the one-ulp-outside points are present
+    np.testing.assert_allclose(ours, expected, rtol=1e-9, atol=1e-10)
+
+
+def test_golden_file_is_what_the_generator_writes() -> None:
+    import importlib.util
+
+    if importlib.util.find_spec("mpmath") is None:
+        return  # the committed values stand on their own; nothing to regenerate with
+
+    script = _GOLDEN_PATH.parent.parent.parent / "scripts" / "gen_truncnorm_golden.py"
+    spec = importlib.util.spec_from_file_location("gen_truncnorm_golden", script)
+    assert spec is not None and spec.loader is not None
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert json.loads(json.dumps(mod.generate())) == _GOLDEN
