@@ -484,7 +484,7 @@ static void launch_mix_logpdf(hipStream_t st, const double* d_x,
                               const double* d_logw, const double* d_steps,
                               const double* d_nchoices, double cat_base,
                               int64_t K, int64_t D, int64_t S, double* d_out,
-                              double* d_scratch) {
+                              double* d_scratch, bool merge = true) {
     const int block = 256;
     const size_t shmem = (4 * (size_t)D + 2 * block) * sizeof(double);
     const int64_t n_chunks = mix_n_chunks(K);
@@ -500,6 +500,8 @@ static void launch_mix_logpdf(hipStream_t st, const double* d_x,
                        dim3(block), shmem, st, d_x, d_xedges, d_c1, d_c2, d_c3,
                        d_logw, d_steps, d_nchoices, cat_base, K, D, MIX_CHUNK,
                        d_part_m, d_part_s);
+    // merge == false: the caller merges the partials itself (fused suggest).
+    if (!merge) return;
     hipLaunchKernelGGL(k_mix_logpdf_merge, dim3((unsigned)S), dim3(64), 0, st,
                        d_part_m, d_part_s, n_chunks, S, d_out);
 }
@@ -553,9 +555,8 @@ struct Workspace {
         }
         pinned_cursor = 0;
     }
-    // memcpy into a fresh pinned slice, then a true-async DMA on the stream.
-    void h2d(void* dst, const void* src, size_t bytes, hipStream_t st) {
-        if (bytes == 0) return;
+    // Reserve a fresh pinned slice (the caller fills it and issues the DMA).
+    char* stage(size_t bytes, hipStream_t st) {
         size_t aligned = (bytes + 255) & ~size_t(255);
         if (pinned_cursor + aligned > pinned_capacity) {
             // Grow: must drain in-flight DMAs that read the old buffer first.
@@ -565,6 +566,12 @@ struct Workspace {
         }
         char* slot = pinned + pinned_cursor;
         pinned_cursor += aligned;
+        return slot;
+    }
+    // memcpy into a fresh pinned slice, then a true-async DMA on the stream.
+    void h2d(void* dst, const void* src, size_t bytes, hipStream_t st) {
+        if (bytes == 0) return;
+        char* slot = stage(bytes, st);
         memcpy(slot, src, bytes);
         HIP_CHECK(hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, st));
     }
@@ -1124,6 +1131,331 @@ __global__ void k_sorted_insert(int32_t* __restrict__ cols,  // (D, cap)
     }
 }
 
+// Same insert without staged positions: the kernel reads each new row's value
+// from the resident table and finds its slot itself with an upper-bound binary
+// search through params[col[j]*D+d] (ties go after equal values and rows are
+// inserted in row order — the host rule side="right"). Row ids are kernel
+// arguments, so nothing is uploaded and the workspace is not touched; stream
+// order alone sequences it against later scoring kernels.
+__global__ void k_sorted_insert_by_value(int32_t* __restrict__ cols,  // (D, cap)
+                                         int64_t cap, int64_t n_sorted,
+                                         const double* __restrict__ params,
+                                         int64_t D, int64_t first_row,
+                                         int64_t n_new) {
+    const int64_t d = blockIdx.x;
+    int32_t* col = cols + d * cap;
+    int64_t n = n_sorted;
+    for (int64_t i = 0; i < n_new; ++i) {
+        const int64_t row = first_row + i;
+        const double v = params[row * D + d];
+        // Block-uniform search: every lane walks the same probes.
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (params[(int64_t)col[mid] * D + d] <= v) lo = mid + 1; else hi = mid;
+        }
+        const int64_t p = lo;
+        __syncthreads();  // all probes done before the shift overwrites cells
+        for (int64_t top = n; top > p; top -= blockDim.x) {
+            const int64_t j = top - 1 - threadIdx.x;
+            int32_t t = 0;
+            if (j >= p) t = col[j];
+            __syncthreads();
+            if (j >= p) col[j + 1] = t;
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) col[p] = (int32_t)row;
+        __syncthreads();
+        ++n;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Fused suggest: the "above" subset is the ascending-row complement of a short
+// sorted exclusion list (below rows + rows invalid for the space), so the
+// subset position of a member row is row - lower_bound(excl, row) and no
+// position map or compaction pass is needed.
+// ---------------------------------------------------------------------------
+
+static constexpr int FUSED_MAX_EXCL = 1024;
+static constexpr int FUSED_MAX_BELOW = 1024;
+static constexpr int FUSED_TILE = 256;
+
+__device__ inline int excl_lower_bound(const int32_t* e, int E, int32_t row) {
+    int lo = 0, hi = E;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] < row) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ inline void write_coeffs(double mu, double sigma, double low,
+                                    double high, bool stepped,
+                                    double* __restrict__ c1,
+                                    double* __restrict__ c2,
+                                    double* __restrict__ c3, int64_t idx) {
+    const double mass =
+        tn::log_gauss_mass((low - mu) / sigma, (high - mu) / sigma);
+    if (stepped) {
+        c1[idx] = mu;
+        c2[idx] = sigma;
+        c3[idx] = -mass;
+    } else {
+        const double inv_var = 1.0 / (sigma * sigma);
+        c1[idx] = -0.5 * inv_var;
+        c2[idx] = mu * inv_var;
+        c3[idx] = -0.5 * mu * mu * inv_var - log(sigma) -
+                  0.9189385332046727418 - mass;
+    }
+}
+
+// Grid (n_tiles + below_tiles, D). Blocks x < n_tiles fit one tile of 256
+// sorted positions of dim y straight from the resident sorted column; the
+// trailing blocks turn the uploaded below (mu, sigma) into coefficients.
+// domain = alow | ahigh | steps | n_choices (D each). logw == nullptr means
+// the caller uploaded custom log-weights; otherwise the dim-0 blocks write the
+// default ramp (numpy linspace arithmetic: k*step + start, uncontracted).
+__global__ void k_fused_fit(const double* __restrict__ params,
+                            const int32_t* __restrict__ sorted,  // (D, s_stride)
+                            int64_t s_stride, int64_t Nv, int64_t n_tiles,
+                            const int32_t* __restrict__ excl, int E,
+                            const double* __restrict__ domain, int64_t Na,
+                            int64_t D, int consider_endpoints, int magic_clip,
+                            double* __restrict__ c1, double* __restrict__ c2,
+                            double* __restrict__ c3, double* __restrict__ logw,
+                            int64_t w_num, double w_start, double w_step,
+                            double log_total, double prior_weight,
+                            const double* __restrict__ bmu,   // (Kb, D)
+                            const double* __restrict__ bsig,  // (Kb, D)
+                            const double* __restrict__ bw,    // (Kb,)
+                            int64_t Kb, double* __restrict__ bc1,
+                            double* __restrict__ bc2, double* __restrict__ bc3,
+                            double* __restrict__ blogw) {
+    __shared__ int32_t s_excl[FUSED_MAX_EXCL];
+    __shared__ int s_prev[FUSED_TILE];
+    __shared__ int s_next[FUSED_TILE];
+    __shared__ double s_val[FUSED_TILE];
+
+    const int64_t d = blockIdx.y;
+    const double low = domain[d];
+    const double high = domain[D + d];
+    const bool stepped = domain[2 * D + d] > 0.0;
+    const double range = high - low;
+    const int i = threadIdx.x;
+
+    if ((int64_t)blockIdx.x >= n_tiles) {
+        // Below estimator: same coefficient formulas, (D, Kb) k-major.
+        const int64_t kb = ((int64_t)blockIdx.x - n_tiles) * FUSED_TILE + i;
+        if (kb < Kb) {
+            write_coeffs(bmu[kb * D + d], bsig[kb * D + d], low, high, stepped,
+                         bc1, bc2, bc3, d * Kb + kb);
+            if (d == 0) blogw[kb] = log(bw[kb]);
+        }
+        return;
+    }
+
+    for (int e = i; e < E; e += FUSED_TILE) s_excl[e] = excl[e];
+    __syncthreads();
+
+    const int64_t K = Na + 1;
+    if (blockIdx.x == 0 && i == 0) {
+        // Prior kernel: midpoint, full-range width.
+        write_coeffs(0.5 * (low + high), range, low, high, stepped, c1, c2, c3,
+                     d * K + Na);
+        if (d == 0 && logw)
+            logw[Na] = (Na == 0) ? 0.0 : log(prior_weight) - log_total;
+    }
+
+    const int32_t* col = sorted + d * s_stride;
+    const int64_t tile0 = (int64_t)blockIdx.x * FUSED_TILE;
+    const int64_t r = tile0 + i;
+    int32_t row = -1;
+    int lb = 0;
+    bool member = false;
+    double mu = 0.0;
+    if (r < Nv) {
+        row = col[r];
+        lb = excl_lower_bound(s_excl, E, row);
+        member = !(lb < E && s_excl[lb] == row);
+        mu = params[(int64_t)row * D + d];
+    }
+    s_val[i] = mu;
+    s_prev[i] = member ? i : -1;
+    s_next[i] = member ? i : FUSED_TILE;
+    __syncthreads();
+    // Inclusive max-scan (last member at or before i) and suffix min-scan
+    // (first member at or after i) over the tile's membership flags.
+    for (int off = 1; off < FUSED_TILE; off <<= 1) {
+        int a = s_prev[i];
+        if (i >= off) a = max(a, s_prev[i - off]);
+        int b = s_next[i];
+        if (i + off < FUSED_TILE) b = min(b, s_next[i + off]);
+        __syncthreads();
+        s_prev[i] = a;
+        s_next[i] = b;
+        __syncthreads();
+    }
+    if (!member) return;
+    const int64_t k = (int64_t)row - lb;
+    if (k >= Na) return;  // inconsistent inputs: never write out of bounds
+
+    const int pi = (i > 0) ? s_prev[i - 1] : -1;
+    const int ni = (i + 1 < FUSED_TILE) ? s_next[i + 1] : FUSED_TILE;
+    bool has_prev = pi >= 0, has_next = ni < FUSED_TILE;
+    double v_prev = has_prev ? s_val[pi] : low;
+    double v_next = has_next ? s_val[ni] : high;
+    // No member on that side of the tile: walk the sorted column past
+    // excluded rows (at most E steps, in practice one).
+    if (!has_prev) {
+        for (int64_t j = tile0 - 1; j >= 0; --j) {
+            const int32_t rj = col[j];
+            const int l = excl_lower_bound(s_excl, E, rj);
+            if (!(l < E && s_excl[l] == rj)) {
+                v_prev = params[(int64_t)rj * D + d];
+                has_prev = true;
+                break;
+            }
+        }
+    }
+    if (!has_next) {
+        for (int64_t j = tile0 + FUSED_TILE; j < Nv; ++j) {
+            const int32_t rj = col[j];
+            const int l = excl_lower_bound(s_excl, E, rj);
+            if (!(l < E && s_excl[l] == rj)) {
+                v_next = params[(int64_t)rj * D + d];
+                has_next = true;
+                break;
+            }
+        }
+    }
+    double minsigma = 1e-12;
+    if (magic_clip) minsigma = range / fmin(100.0, (double)(Na + 2));
+    double sigma = fmax(mu - v_prev, v_next - mu);
+    if (!consider_endpoints && Na >= 2) {
+        if (!has_prev) {
+            sigma = v_next - mu;
+        } else if (!has_next) {
+            sigma = mu - v_prev;
+        }
+    }
+    sigma = fmin(fmax(sigma, minsigma), range);
+    write_coeffs(mu, sigma, low, high, stepped, c1, c2, c3, d * K + k);
+    if (d == 0 && logw) {
+        double w = 1.0;
+        if (k < w_num) {
+            w = (w_num > 1 && k == w_num - 1)
+                    ? 1.0
+                    : __dadd_rn(__dmul_rn((double)k, w_step), w_start);
+        }
+        logw[k] = log(w) - log_total;
+    }
+}
+
+// Block-wide merge of per-thread online-logsumexp states; the result lands
+// in red_m[0] / red_s[0]. blockDim.x must be a power of two.
+__device__ inline void block_lse_merge(double* red_m, double* red_s, double m,
+                                       double acc) {
+    red_m[threadIdx.x] = m;
+    red_s[threadIdx.x] = acc;
+    __syncthreads();
+    for (int stride = blockDim.x / 2; stride > 0; stride >>= 1) {
+        if (threadIdx.x < stride) {
+            double m2 = red_m[threadIdx.x + stride];
+            double s2 = red_s[threadIdx.x + stride];
+            double m1 = red_m[threadIdx.x];
+            double s1 = red_s[threadIdx.x];
+            if (m2 > m1) {
+                s1 = s1 * exp(m1 - m2) + s2;
+                m1 = m2;
+            } else if (m1 != -INFINITY) {
+                s1 = s1 + s2 * exp(m2 - m1);
+            }
+            red_m[threadIdx.x] = m1;
+            red_s[threadIdx.x] = s1;
+        }
+        __syncthreads();
+    }
+}
+
+// Merge stage of the fused suggest, one block per candidate: merges the above
+// partials into log g (n_chunks == 0: log g was already written to logg_in by
+// the single-phase kernel), evaluates the below mixture's logsumexp over its
+// <= 1024 kernels, and writes out = [log l - log g | log g | log l] (3, S).
+__global__ void k_mix_merge_ei(const double* __restrict__ part_m,
+                               const double* __restrict__ part_s,
+                               int64_t n_chunks, int64_t S,
+                               const double* __restrict__ logg_in,
+                               const double* __restrict__ x,       // (S, D)
+                               const double* __restrict__ xedges,  // (S, 2D)
+                               const double* __restrict__ bc1,
+                               const double* __restrict__ bc2,
+                               const double* __restrict__ bc3,
+                               const double* __restrict__ blogw,
+                               const double* __restrict__ steps,
+                               const double* __restrict__ n_choices,
+                               int64_t Kb, int64_t D,
+                               double* __restrict__ out) {
+    extern __shared__ double lds[];
+    double* xs = lds;
+    double* x2 = lds + D;
+    double* xl = lds + 2 * D;
+    double* xr = lds + 3 * D;
+    double* red_m = lds + 4 * D;
+    double* red_s = red_m + blockDim.x;
+
+    const int64_t s = blockIdx.x;
+    for (int64_t d = threadIdx.x; d < D; d += blockDim.x) {
+        const double v = x[s * D + d];
+        xs[d] = v;
+        x2[d] = v * v;
+        xl[d] = xedges[s * 2 * D + d];
+        xr[d] = xedges[s * 2 * D + D + d];
+    }
+
+    double log_g;
+    if (n_chunks > 0) {
+        double m = -INFINITY, acc = 0.0;
+        for (int64_t c = threadIdx.x; c < n_chunks; c += blockDim.x) {
+            const double m2 = part_m[c * S + s];
+            const double s2 = part_s[c * S + s];
+            if (m2 > m) {
+                acc = acc * exp(m - m2) + s2;
+                m = m2;
+            } else if (m != -INFINITY) {
+                acc += s2 * exp(m2 - m);
+            }
+        }
+        block_lse_merge(red_m, red_s, m, acc);
+        log_g = (red_m[0] == -INFINITY) ? -INFINITY : red_m[0] + log(red_s[0]);
+    } else {
+        log_g = logg_in[s];
+    }
+    __syncthreads();  // xs staged; red_* free for reuse
+
+    double m = -INFINITY, acc = 0.0;
+    for (int64_t k = threadIdx.x; k < Kb; k += blockDim.x) {
+        double t = blogw[k];
+        for (int64_t d = 0; d < D; ++d)
+            t += mix_term(bc1, bc2, bc3, steps, n_choices, 0.0, xs, x2, xl, xr,
+                          Kb, k, d);
+        if (t > m) {
+            acc = acc * exp(m - t) + 1.0;
+            m = t;
+        } else if (m != -INFINITY) {
+            acc += exp(t - m);
+        }
+    }
+    block_lse_merge(red_m, red_s, m, acc);
+    if (threadIdx.x == 0) {
+        const double log_l =
+            (red_m[0] == -INFINITY) ? -INFINITY : red_m[0] + log(red_s[0]);
+        out[s] = log_l - log_g;
+        out[S + s] = log_g;
+        out[2 * S + s] = log_l;
+    }
+}
+
 using arr_i32 = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
 
 class TpeDeviceHistory {
@@ -1133,6 +1465,7 @@ class TpeDeviceHistory {
     ~TpeDeviceHistory() {
         if (params_) (void)hipFree(params_);
         if (sorted_) (void)hipFree(sorted_);
+        if (domain_) (void)hipFree(domain_);
     }
 
     int64_t n_rows() const { return n_; }
@@ -1372,6 +1705,209 @@ class TpeDeviceHistory {
 
     int64_t n_sorted() const { return sorted_valid_ ? n_sorted_ : -1; }
 
+    // Insert table rows [first_row, first_row + n_new) into the resident index
+    // by value (see k_sorted_insert_by_value). No upload, no sync.
+    void insert_sorted_by_value(int64_t first_row, int64_t n_new) {
+        if (!sorted_valid_)
+            throw std::runtime_error("insert_sorted_by_value before upload");
+        if (n_new <= 0) return;
+        if (first_row < 0 || first_row + n_new > n_)
+            throw std::runtime_error("insert_sorted_by_value: rows not in table");
+        hipStream_t st = g_ws.get_stream();
+        ensure_sorted_capacity(n_sorted_ + n_new, st);
+        hipLaunchKernelGGL(k_sorted_insert_by_value, dim3((unsigned)D_),
+                           dim3(256), 0, st, sorted_, sorted_cap_, n_sorted_,
+                           params_, D_, first_row, n_new);
+        HIP_CHECK(hipGetLastError());
+        n_sorted_ += n_new;
+    }
+
+    // Debug/test accessor: the resident sorted index as a (D, n_sorted) array.
+    py::array_t<int32_t> sorted_index() {
+        if (!sorted_valid_) throw std::runtime_error("sorted_index before upload");
+        py::array_t<int32_t> out({D_, n_sorted_});
+        hipStream_t st = g_ws.get_stream();
+        if (n_sorted_ > 0)
+            HIP_CHECK(hipMemcpy2DAsync(out.mutable_data(), (size_t)n_sorted_ * 4,
+                                       sorted_, (size_t)sorted_cap_ * 4,
+                                       (size_t)n_sorted_ * 4, (size_t)D_,
+                                       hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return out;
+    }
+
+    // Per-space constants (KDE-domain bounds, steps, category counts): they
+    // never change for a (study, search-space), so they are uploaded once.
+    void set_domain(const arr_f64& alow, const arr_f64& ahigh,
+                    const arr_f64& steps, const arr_f64& n_choices) {
+        if ((int64_t)alow.size() != D_ || (int64_t)ahigh.size() != D_ ||
+            (int64_t)steps.size() != D_ || (int64_t)n_choices.size() != D_)
+            throw std::runtime_error("set_domain: shape mismatch");
+        std::vector<double> host(4 * (size_t)D_);
+        std::copy(alow.data(), alow.data() + D_, host.begin());
+        std::copy(ahigh.data(), ahigh.data() + D_, host.begin() + D_);
+        std::copy(steps.data(), steps.data() + D_, host.begin() + 2 * D_);
+        std::copy(n_choices.data(), n_choices.data() + D_, host.begin() + 3 * D_);
+        hipStream_t st = g_ws.get_stream();
+        if (!domain_) HIP_CHECK(hipMalloc(&domain_, host.size() * sizeof(double)));
+        // Earlier launches may still read the old values.
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipMemcpy(domain_, host.data(), host.size() * sizeof(double),
+                            hipMemcpyHostToDevice));
+        has_steps_ = false;
+        has_categorical_ = false;
+        for (int64_t d = 0; d < D_; ++d) {
+            has_steps_ |= steps.data()[d] > 0.0;
+            has_categorical_ |= n_choices.data()[d] > 0.0;
+        }
+    }
+
+    // Fused suggest: one packed upload, fit + below coefficients in one
+    // launch, scoring, and below log-pdf / EI in the merge stage.
+    //   excl     sorted table rows NOT in the above set (below + invalid rows)
+    //   n_above  size of the above set (= resident index rows not in excl)
+    //   x/xedges candidates (KDE domain); xedges only read for stepped dims
+    //   bmu/bsig/bw  below estimator kernels (Kb, D) and mixture weights (Kb,)
+    //   logw     custom above log-weights (n_above + 1,), or empty for the
+    //            default ramp, which the device writes itself from
+    //            (w_num, w_start, w_step, log_total)
+    // Returns (S,) log l - log g.
+    py::object fused_score(const arr_i32& excl, int64_t n_above,
+                                    const arr_f64& x, const arr_f64& xedges,
+                                    const arr_f64& bmu, const arr_f64& bsig,
+                                    const arr_f64& bw, const arr_f64& logw,
+                                    int64_t w_num, double w_start,
+                                    double w_step, double log_total,
+                                    double prior_weight,
+                                    bool consider_endpoints, bool magic_clip,
+                                    bool return_parts) {
+        if (!sorted_valid_) throw std::runtime_error("fused_score before upload_sorted");
+        if (!domain_) throw std::runtime_error("fused_score before set_domain");
+        if (has_categorical_)
+            throw std::runtime_error("fused_score: categorical dims unsupported");
+        if (x.ndim() != 2 || x.shape(1) != D_ || bmu.ndim() != 2 ||
+            bmu.shape(1) != D_ || bsig.ndim() != 2 || bsig.shape(1) != D_)
+            throw std::runtime_error("fused_score: shape mismatch");
+        const int64_t S = x.shape(0);
+        const int64_t Kb = bmu.shape(0);
+        const int64_t E = excl.size();
+        const int64_t Na = n_above;
+        const int64_t K = Na + 1;
+        const int64_t Nv = n_sorted_;
+        const bool custom_w = logw.size() > 0;
+        if (S < 1 || Kb < 1 || Kb > FUSED_MAX_BELOW || bsig.shape(0) != Kb ||
+            (int64_t)bw.size() != Kb || E > FUSED_MAX_EXCL || Na < 0 ||
+            Na > Nv || Na + E < Nv || (custom_w && (int64_t)logw.size() != K) ||
+            (has_steps_ && (int64_t)xedges.size() != 2 * S * D_))
+            throw std::runtime_error("fused_score: shape mismatch");
+        // Strictly ascending in-table rows: keeps row - lower_bound(excl, row)
+        // inside [0, n_above) for every member row.
+        const int32_t* ex = excl.data();
+        for (int64_t e = 0; e < E; ++e)
+            if (ex[e] < 0 || ex[e] >= n_ || (e > 0 && ex[e] <= ex[e - 1]))
+                throw std::runtime_error("fused_score: excl must be sorted table rows");
+
+        hipStream_t st = g_ws.get_stream();
+        // Packed region (one pinned slice, one DMA, same layout on device):
+        //   x | bmu | bsig | bw | [logw] | excl (i32, padded) | [xedges]
+        // The xedges slot is always reserved on device (the scoring kernels
+        // stage it unconditionally) but only uploaded when a dim is stepped.
+        const size_t n_x = (size_t)S * D_;
+        const size_t n_b = (size_t)Kb * D_;
+        const size_t n_excl = ((size_t)E + 1) / 2;
+        const size_t n_logw_up = custom_w ? (size_t)K : 0;
+        const size_t up_doubles =
+            n_x + 2 * n_b + Kb + n_logw_up + n_excl + (has_steps_ ? 2 * n_x : 0);
+        const size_t packed_doubles = n_x + 2 * n_b + Kb + n_logw_up + n_excl + 2 * n_x;
+        const size_t n_c = (size_t)K * D_;
+        const int64_t n_chunks = mix_n_chunks(K);
+        const size_t n_scratch = 2 * (size_t)n_chunks * S;
+        double* base = g_ws.ensure(packed_doubles + 3 * n_c + K + 3 * n_b + Kb +
+                                   n_scratch + 4 * (size_t)S + 16);
+        double* d_x = base;
+        double* d_bmu = d_x + n_x;
+        double* d_bsig = d_bmu + n_b;
+        double* d_bw = d_bsig + n_b;
+        double* d_logw_up = d_bw + Kb;
+        int32_t* d_excl = reinterpret_cast<int32_t*>(d_logw_up + n_logw_up);
+        double* d_xedges = d_logw_up + n_logw_up + n_excl;
+        double* d_c1 = base + packed_doubles;
+        double* d_c2 = d_c1 + n_c;
+        double* d_c3 = d_c2 + n_c;
+        double* d_logw = d_c3 + n_c;
+        double* d_bc1 = d_logw + K;
+        double* d_bc2 = d_bc1 + n_b;
+        double* d_bc3 = d_bc2 + n_b;
+        double* d_blogw = d_bc3 + n_b;
+        double* d_scratch = d_blogw + Kb;
+        double* d_logg = d_scratch + n_scratch;
+        double* d_out = d_logg + S;
+
+        g_ws.begin_uploads();
+        {
+            double* h = reinterpret_cast<double*>(g_ws.stage(up_doubles * 8, st));
+            double* p = h;
+            memcpy(p, x.data(), n_x * 8); p += n_x;
+            memcpy(p, bmu.data(), n_b * 8); p += n_b;
+            memcpy(p, bsig.data(), n_b * 8); p += n_b;
+            memcpy(p, bw.data(), (size_t)Kb * 8); p += Kb;
+            if (custom_w) { memcpy(p, logw.data(), (size_t)K * 8); p += K; }
+            if (n_excl) {
+                p[n_excl - 1] = 0.0;  // defined padding for odd E
+                memcpy(p, ex, (size_t)E * 4);
+                p += n_excl;
+            }
+            if (has_steps_) memcpy(p, xedges.data(), 2 * n_x * 8);
+            HIP_CHECK(hipMemcpyAsync(base, h, up_doubles * 8,
+                                     hipMemcpyHostToDevice, st));
+        }
+
+        const double* d_steps = domain_ + 2 * D_;
+        const double* d_nchoices = domain_ + 3 * D_;
+        const int64_t n_tiles = std::max<int64_t>(1, (Nv + FUSED_TILE - 1) / FUSED_TILE);
+        const int64_t b_tiles = (Kb + FUSED_TILE - 1) / FUSED_TILE;
+        hipLaunchKernelGGL(k_fused_fit,
+                           dim3((unsigned)(n_tiles + b_tiles), (unsigned)D_),
+                           dim3(FUSED_TILE), 0, st, params_, sorted_, sorted_cap_,
+                           Nv, n_tiles, d_excl, (int)E, domain_, Na, D_,
+                           consider_endpoints ? 1 : 0, magic_clip ? 1 : 0, d_c1,
+                           d_c2, d_c3, custom_w ? nullptr : d_logw, w_num,
+                           w_start, w_step, log_total, prior_weight, d_bmu,
+                           d_bsig, d_bw, Kb, d_bc1, d_bc2, d_bc3, d_blogw);
+        const double* d_logw_use = custom_w ? d_logw_up : d_logw;
+        const double cat_base = prior_weight / (double)K;
+        launch_mix_logpdf(st, d_x, d_xedges, d_c1, d_c2, d_c3, d_logw_use,
+                          d_steps, d_nchoices, cat_base, K, D_, S, d_logg,
+                          d_scratch, /*merge=*/false);
+        {
+            const int block = 256;
+            const size_t shmem = (4 * (size_t)D_ + 2 * block) * sizeof(double);
+            hipLaunchKernelGGL(k_mix_merge_ei, dim3((unsigned)S), dim3(block),
+                               shmem, st, d_scratch, d_scratch + (size_t)n_chunks * S,
+                               n_chunks > 1 ? n_chunks : 0, S, d_logg, d_x,
+                               d_xedges, d_bc1, d_bc2, d_bc3, d_blogw, d_steps,
+                               d_nchoices, Kb, D_, d_out);
+        }
+        if (return_parts) {
+            // Test/debug form: ((3, S) [ei | log g | log l], (K,) above logw).
+            py::array_t<double> parts({(int64_t)3, S});
+            py::array_t<double> lw(K);
+            HIP_CHECK(hipMemcpyAsync(parts.mutable_data(), d_out, 3 * (size_t)S * 8,
+                                     hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(lw.mutable_data(), d_logw_use, (size_t)K * 8,
+                                     hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            HIP_CHECK(hipGetLastError());
+            return py::make_tuple(parts, lw);
+        }
+        py::array_t<double> out(S);
+        HIP_CHECK(hipMemcpyAsync(out.mutable_data(), d_out, (size_t)S * 8,
+                                 hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipGetLastError());
+        return out;
+    }
+
   private:
     void ensure_sorted_capacity(int64_t need, hipStream_t st) {
         if (need <= sorted_cap_) return;
@@ -1398,6 +1934,9 @@ class TpeDeviceHistory {
     int64_t n_sorted_ = 0;
     int64_t sorted_cap_ = 0;
     bool sorted_valid_ = false;
+    double* domain_ = nullptr;  // alow | ahigh | steps | n_choices
+    bool has_steps_ = false;
+    bool has_categorical_ = false;
 };
 
 
@@ -2142,6 +2681,19 @@ PYBIND11_MODULE(_hipcore, m) {
         .def("insert_sorted", &TpeDeviceHistory::insert_sorted, py::arg("pos"),
              py::arg("rows"))
         .def_property_readonly("n_sorted", &TpeDeviceHistory::n_sorted)
+        .def("insert_sorted_by_value", &TpeDeviceHistory::insert_sorted_by_value,
+             py::arg("first_row"), py::arg("n_new"))
+        .def("sorted_index", &TpeDeviceHistory::sorted_index)
+        .def("set_domain", &TpeDeviceHistory::set_domain, py::arg("alow"),
+             py::arg("ahigh"), py::arg("steps"), py::arg("n_choices"))
+        .def("fused_score", &TpeDeviceHistory::fused_score, py::arg("excl"),
+             py::arg("n_above"), py::arg("x"), py::arg("xedges"),
+             py::arg("bmu"), py::arg("bsig"), py::arg("bw"),
+             py::arg("logw") = arr_f64(), py::arg("w_num") = 0,
+             py::arg("w_start") = 1.0, py::arg("w_step") = 0.0,
+             py::arg("log_total") = 0.0, py::arg("prior_weight") = 1.0,
+             py::arg("consider_endpoints") = false,
+             py::arg("magic_clip") = true, py::arg("return_parts") = false)
         .def("score", &TpeDeviceHistory::score, py::arg("sorted_rows"),
              py::arg("pos"), py::arg("n_above"), py::arg("logw"), py::arg("alow"),
              py::arg("ahigh"), py::arg("steps"), py::arg("n_choices"),

@@ -1,6 +1,6 @@
 """Device dispatch for the TPE hot path (K1 fit + K2 mixture log-pdf on gfx950).
 
-Two device modes:
+Three device modes:
 
 * **Resident history** (the fast path): each (study, search-space) keeps a
   ``TpeDeviceHistory`` whose parameter table lives in HBM and grows append-only
@@ -8,6 +8,11 @@ Two device modes:
   per-dim sorted order (i32), a subset position map, the mixture weights and the
   24 candidates — the fp64 observation matrix never crosses PCIe again. Subset
   compaction, the K1 fit and the K2 scoring all run on device.
+* **Fused suggest** (`fused_eligible`): for joint scoring over numerical dims the
+  whole suggest is one native call — a single packed upload (candidates, the
+  below estimator's kernels, the short list of excluded rows), a fit straight
+  from the resident sorted index, scoring, and the below log-pdf and EI
+  difference in the merge stage. No O(N) array is built or uploaded.
 * **Stateless scoring** (`kde_logpdf`): used by golden tests and the
   constant-liar path (whose observation set includes rows not in the table).
 
@@ -18,7 +23,8 @@ dimensions keep the (already vectorized) host path.
 from __future__ import annotations
 
 import math
-from typing import TYPE_CHECKING
+import os
+from typing import TYPE_CHECKING, NamedTuple
 
 import numpy as np
 
@@ -46,6 +52,91 @@ def space_is_device_eligible(space: dict[str, BaseDistribution]) -> bool:
 
 def device_ready(n_kernels: int) -> bool:
     return n_kernels >= DEVICE_MIN_KERNELS and _hip.is_available()
+
+
+# Limits of the fused entry point (LDS-cached exclusion list, below kernels
+# evaluated by one block per candidate); mirrored in tpe_core.hip.
+FUSED_MAX_EXCL = 1024
+FUSED_MAX_BELOW = 1024
+
+_EMPTY_F64 = np.empty(0, dtype=np.float64)
+
+
+def fused_enabled() -> bool:
+    """``OPTUNA_AMD_TPE_FUSED=0`` forces the unfused path (A/B runs)."""
+    return os.environ.get("OPTUNA_AMD_TPE_FUSED", "1") != "0"
+
+
+def fused_eligible(
+    space: dict[str, BaseDistribution],
+    *,
+    per_dim: bool,
+    n_liar: int,
+    default_estimator: bool,
+    rows_ascending: bool,
+    n_excl: int,
+    n_below_kernels: int,
+) -> bool:
+    """Whether a suggest may take the fused device entry point.
+
+    The fused kernels address the "above" set as the ascending-row complement
+    of a short exclusion list, score jointly, and evaluate the below mixture
+    inside the merge stage; every other case keeps the unfused path.
+    """
+    return (
+        fused_enabled()
+        and not per_dim
+        and n_liar == 0
+        and default_estimator
+        and rows_ascending
+        and n_excl <= FUSED_MAX_EXCL
+        and n_below_kernels <= FUSED_MAX_BELOW
+        and bool(space)
+        and not any(isinstance(d, CategoricalDistribution) for d in space.values())
+    )
+
+
+def default_weight_ramp(n: int, prior_weight: float) -> tuple[int, float, float, float]:
+    """(w_num, w_start, w_step, log_total) describing ``default_weights(n)``
+    plus the prior weight, for the device to expand: kernel k < w_num has
+    weight ``k * w_step + w_start`` (numpy ``linspace`` arithmetic, last ramp
+    element exactly 1), every later kernel 1, the prior ``prior_weight``;
+    ``log_total`` is the log of their sum (arithmetic series, O(1))."""
+    if n < 25:
+        return 0, 1.0, 0.0, math.log(n + prior_weight) if n else 0.0
+    num = n - 25
+    start = 1.0 / n
+    step = (1.0 - start) / (num - 1) if num > 1 else 0.0
+    if num > 1:
+        ramp_sum = num * (start + 1.0) / 2.0
+    else:
+        ramp_sum = start * num
+    return num, start, step, math.log(ramp_sum + 25.0 + prior_weight)
+
+
+def expand_weight_ramp(n: int, prior_weight: float) -> np.ndarray:
+    """Host transcription of the device's expansion of ``default_weight_ramp``:
+    the (n + 1,) unnormalized mixture weights, prior last (the device then
+    writes ``log(w) - log_total``). Used by the tests."""
+    num, start, step, _ = default_weight_ramp(n, prior_weight)
+    w = np.ones(n + 1, dtype=np.float64)
+    k = np.arange(num, dtype=np.float64)
+    w[:num] = k * step + start
+    if num > 1:
+        w[num - 1] = 1.0
+    w[n] = prior_weight if n else 1.0
+    return w
+
+
+class FusedRequest(NamedTuple):
+    """Inputs of a fused suggest beyond those of ``score_above_resident``."""
+
+    below_rows: np.ndarray  # table rows of the below set
+    n_above: int  # valid rows outside the below set
+    x_raw: np.ndarray  # (S, D) candidates, as drawn
+    below_mus: np.ndarray  # (Kb, D) below estimator kernels, KDE domain
+    below_sigmas: np.ndarray  # (Kb, D)
+    below_weights: np.ndarray  # (Kb,)
 
 
 def _space_domains(
@@ -128,11 +219,12 @@ class _SpaceDeviceMirror:
             self._n_choices,
         ) = _space_domains(space)
         self._hist = core.TpeDeviceHistory(len(space))
+        self._hist.set_domain(self._alow, self._ahigh, self._steps, self._n_choices)
+        self._has_steps = bool((self._steps > 0).any())
         self._n_appended = 0
-        # Device-resident sorted index bookkeeping: entries of the host cache's
-        # insert log already replayed, and the resident index length.
-        self._sorted_log_cursor = 0
-        self._n_sorted_synced = -1
+        # Device-resident sorted index bookkeeping: table rows the resident
+        # index already covers (-1: never uploaded).
+        self._rows_sorted_synced = -1
 
     def sync(self, cache: "_SpaceCache") -> None:
         n_total = len(cache.valid)
@@ -146,24 +238,30 @@ class _SpaceDeviceMirror:
         self._sync_sorted(cache)
 
     def _sync_sorted(self, cache: "_SpaceCache") -> None:
-        log = cache._insert_log
-        if self._n_sorted_synced == cache._n_sorted:
+        n_rows = len(cache.valid)
+        done = self._rows_sorted_synced
+        if done == n_rows:
             return
-        pending = log[self._sorted_log_cursor :]
         # Bulk (re-)upload when starting fresh or when a large batch arrived
-        # (the sequential device insert is O(batch · N)); per-tell single-row
-        # inserts replay incrementally.
-        if (
-            self._n_sorted_synced < 0
-            or len(pending) > 16
-            or any(len(rows) > 64 for _, rows in pending)
-        ):
+        # (the sequential device insert is O(batch · N)); per-tell rows are
+        # inserted by value on device, which needs neither the host index nor
+        # an upload. (Log dims compare log values there: two rows a few ulps
+        # apart may tie after the log and then keep row order.)
+        if done < 0 or n_rows - done > 64:
             self._hist.upload_sorted(list(cache.sorted_rows))
         else:
-            for pos, rows in pending:
-                self._hist.insert_sorted(pos, rows)
-        self._sorted_log_cursor = len(log)
-        self._n_sorted_synced = cache._n_sorted
+            valid = cache.valid[done:n_rows]
+            r = 0
+            while r < len(valid):
+                if not valid[r]:
+                    r += 1
+                    continue
+                e = r
+                while e < len(valid) and valid[e]:
+                    e += 1
+                self._hist.insert_sorted_by_value(done + r, e - r)
+                r = e
+        self._rows_sorted_synced = n_rows
 
     def score(
         self,
@@ -189,12 +287,8 @@ class _SpaceDeviceMirror:
         pos = np.full(n_total, -1, dtype=np.int32)
         pos[sel] = np.arange(len(sel), dtype=np.int32)
         # The per-dim sorted index is device-resident (kept current by
-        # _sync_sorted); pass no columns unless the resident copy somehow
-        # lagged, in which case fall back to a one-off upload.
-        if self._n_sorted_synced == cache._n_sorted:
-            sorted_cols: list = []
-        else:
-            sorted_cols = list(cache.sorted_rows)
+        # _sync_sorted), so no columns are passed.
+        sorted_cols: list = []
         x_raw = np.column_stack(
             [np.asarray(samples[n], dtype=np.float64) for n in cache.names]
         )
@@ -238,25 +332,84 @@ class _SpaceDeviceMirror:
         )
 
 
+    def score_fused(
+        self,
+        cache: "_SpaceCache",
+        req: FusedRequest,
+        weights: np.ndarray | None,
+        consider_endpoints: bool,
+        consider_magic_clip: bool,
+        prior_weight: float,
+        return_parts: bool = False,
+    ) -> np.ndarray:
+        """Acquisition values through the fused entry point: one packed
+        upload, no O(N) host arrays. ``weights`` is the normalized (n_above+1,)
+        mixture weight vector of a custom weights function, or None for the
+        default ramp."""
+        self.sync(cache)
+        excl = cache.excluded_rows(req.below_rows)
+        x = req.x_raw
+        xedges = _cell_edges(x, self._is_log, self._steps) if self._has_steps else _EMPTY_F64
+        if self._is_log.any():
+            x = x.copy()
+            x[:, self._is_log] = np.log(x[:, self._is_log])
+        if weights is None:
+            logw = _EMPTY_F64
+            w_num, w_start, w_step, log_total = default_weight_ramp(
+                req.n_above, prior_weight
+            )
+        else:
+            with np.errstate(divide="ignore"):
+                logw = np.log(weights)
+            w_num, w_start, w_step, log_total = 0, 1.0, 0.0, 0.0
+        return self._hist.fused_score(
+            excl,
+            int(req.n_above),
+            x,
+            xedges,
+            req.below_mus,
+            req.below_sigmas,
+            req.below_weights,
+            logw,
+            w_num,
+            w_start,
+            w_step,
+            log_total,
+            float(prior_weight),
+            consider_endpoints,
+            consider_magic_clip,
+            return_parts,
+        )
+
+
 def score_above_resident(
     cache: "_SpaceCache",
-    sel: np.ndarray,
-    weights: np.ndarray,
-    samples: dict[str, np.ndarray],
+    sel: np.ndarray | None,
+    weights: np.ndarray | None,
+    samples: dict[str, np.ndarray] | None,
     consider_endpoints: bool,
     consider_magic_clip: bool,
     prior_weight: float = 1.0,
     extras: np.ndarray | None = None,
     per_dim: bool = False,
+    fused: FusedRequest | None = None,
 ) -> np.ndarray:
     """log g(x) for candidates via the device-resident table (creates the mirror
     on first use; attached to the host space cache so lifetimes match).
     ``per_dim=True`` returns the (S, D) per-dimension 1-D mixture log-pdfs
-    (independent-mode TPE) instead of the joint (S,) product score."""
+    (independent-mode TPE) instead of the joint (S,) product score.
+
+    With ``fused`` (see ``fused_eligible``) the call returns the acquisition
+    values ``log l(x) - log g(x)`` instead; ``sel`` and ``samples`` are unused
+    and ``weights=None`` selects the default weight ramp, written on device."""
     mirror = getattr(cache, "_device_mirror", None)
     if mirror is None:
         mirror = _SpaceDeviceMirror(cache.space)
         cache._device_mirror = mirror  # type: ignore[attr-defined]
+    if fused is not None:
+        return mirror.score_fused(
+            cache, fused, weights, consider_endpoints, consider_magic_clip, prior_weight
+        )
     return mirror.score(
         cache, sel, weights, samples, consider_endpoints, consider_magic_clip,
         prior_weight=prior_weight, extras=extras, per_dim=per_dim,

@@ -59,14 +59,24 @@ class _SpaceCache:
         # reallocation per dimension per suggest.
         # Rows as int32: the device compaction kernels consume these columns
         # directly (contiguous per-dim prefixes, no per-suggest restack/cast).
-        self._n_sorted = 0
+        # The host index is maintained lazily: `append` only records the new
+        # valid rows, and the accessors below (`sorted_vals`, `sorted_rows`,
+        # `_insert_log`, `_n_sorted`) replay the backlog first. A suggest that
+        # runs on the device-resident index never pays the per-dim tail shifts.
+        self._n_sorted_host = 0
         self._vals_buf = [np.empty(64, dtype=np.float64) for _ in self.names]
         self._rows_buf = [np.empty(64, dtype=np.int32) for _ in self.names]
         # Insert log for the device-resident sorted index: per append, the
         # FINAL insert position and row id per dim (consumed by the GPU mirror
         # so each suggest replays O(new) inserts instead of re-uploading the
         # whole (Nv, D) order).
-        self._insert_log: list[tuple[np.ndarray, np.ndarray]] = []
+        self._insert_log_host: list[tuple[np.ndarray, np.ndarray]] = []
+        self._pending: list[np.ndarray] = []  # valid rows per append, unflushed
+        # Non-flushing counters: valid rows so far, and the invalid row ids
+        # (rows whose trial lacks a parameter of the space), ascending.
+        self.n_valid = 0
+        self._invalid_rows: list[int] = []
+        self._invalid_arr = np.empty(0, dtype=np.int32)
 
     @property
     def params(self) -> np.ndarray:
@@ -78,11 +88,38 @@ class _SpaceCache:
 
     @property
     def sorted_vals(self) -> list[np.ndarray]:
-        return [b[: self._n_sorted] for b in self._vals_buf]
+        self._flush()
+        return [b[: self._n_sorted_host] for b in self._vals_buf]
 
     @property
     def sorted_rows(self) -> list[np.ndarray]:
-        return [b[: self._n_sorted] for b in self._rows_buf]
+        self._flush()
+        return [b[: self._n_sorted_host] for b in self._rows_buf]
+
+    @property
+    def _n_sorted(self) -> int:
+        self._flush()
+        return self._n_sorted_host
+
+    @property
+    def _insert_log(self) -> list[tuple[np.ndarray, np.ndarray]]:
+        self._flush()
+        return self._insert_log_host
+
+    @property
+    def n_invalid(self) -> int:
+        return len(self._invalid_rows)
+
+    def excluded_rows(self, below_rows: np.ndarray) -> np.ndarray:
+        """Sorted int32 table rows outside the "above" set when that set is the
+        ascending-row complement of ``below_rows``: the below rows plus the
+        rows invalid for this space. O(n_below + n_invalid)."""
+        excl = np.sort(np.asarray(below_rows)).astype(np.int32)
+        if self._invalid_rows:
+            if len(self._invalid_arr) != len(self._invalid_rows):
+                self._invalid_arr = np.asarray(self._invalid_rows, dtype=np.int32)
+            excl = np.union1d(excl, self._invalid_arr)
+        return excl
 
     def append(self, trials: Sequence[FrozenTrial]) -> None:
         n_new = len(trials)
@@ -113,9 +150,24 @@ class _SpaceCache:
 
         new_rows = base + np.nonzero(valid)[0]
         m = len(new_rows)
+        if m < n_new:
+            self._invalid_rows.extend((base + np.nonzero(~valid)[0]).tolist())
         if m == 0:
             return
-        n = self._n_sorted
+        self.n_valid += m
+        self._pending.append(new_rows)
+
+    def _flush(self) -> None:
+        """Bring the host sorted index up to date, one recorded append at a
+        time (so the arrays and the insert log equal eager maintenance)."""
+        if self._pending:
+            pending, self._pending = self._pending, []
+            for new_rows in pending:
+                self._insert_sorted(new_rows)
+
+    def _insert_sorted(self, new_rows: np.ndarray) -> None:
+        m = len(new_rows)
+        n = self._n_sorted_host
         if n + m > len(self._vals_buf[0]):
             cap = max(2 * len(self._vals_buf[0]), n + m)
             for c in range(len(self.names)):
@@ -164,8 +216,8 @@ class _SpaceCache:
                 # pos[j] + j in the merged array.
                 log_pos[:, c] = pos + np.arange(m)
                 log_rows[:, c] = rows_sorted
-        self._insert_log.append((log_pos, log_rows))
-        self._n_sorted = n + m
+        self._insert_log_host.append((log_pos, log_rows))
+        self._n_sorted_host = n + m
 
     _shift_scratch: tuple[np.ndarray, np.ndarray] | None = None
 
@@ -490,14 +542,21 @@ class _TpeHistory:
         return cache
 
     def valid_rows(
-        self, space: dict[str, BaseDistribution], row_indices: np.ndarray
+        self,
+        space: dict[str, BaseDistribution],
+        row_indices: np.ndarray,
+        cache: _SpaceCache | None = None,
     ) -> np.ndarray:
         """Subset of row_indices whose trials define every parameter of the space."""
-        cache = self.space_cache(space)
+        if cache is None:
+            cache = self.space_cache(space)
         return row_indices[cache.valid[row_indices]]
 
     def observations(
-        self, space: dict[str, BaseDistribution], row_indices: np.ndarray
+        self,
+        space: dict[str, BaseDistribution],
+        row_indices: np.ndarray,
+        cache: _SpaceCache | None = None,
     ) -> tuple[dict[str, np.ndarray], dict[str, np.ndarray]]:
         """Row-gather the observation matrix for a trial subset.
 
@@ -505,7 +564,8 @@ class _TpeHistory:
         order, plus per-param argsort arrays derived from the incrementally-sorted
         index (no per-call sort).
         """
-        cache = self.space_cache(space)
+        if cache is None:
+            cache = self.space_cache(space)
         sel = row_indices[cache.valid[row_indices]]
         mat = cache.params[sel]
         obs = {name: mat[:, c] for c, name in enumerate(cache.names)}

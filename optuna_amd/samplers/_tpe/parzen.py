@@ -128,7 +128,6 @@ class _ParzenEstimator:
                 observations, dists, parameters, n_obs
             )
             self._categoricals = []
-            self._precompute_logpdf_coefficients()
             return
 
         num_idx: list[int] = []
@@ -203,7 +202,18 @@ class _ParzenEstimator:
             ),
         )
         self._categoricals = categoricals
-        self._precompute_logpdf_coefficients()
+
+    # Scoring coefficients are derived on first use: an estimator that only
+    # draws candidates (its kernels are scored on device) never pays for them.
+    _LAZY_COEFFICIENTS = frozenset(
+        ("_cont_mask", "_log_total_mass", "_c1", "_c2", "_c3", "_c3_rowsum")
+    )
+
+    def __getattr__(self, name: str):
+        if name in _ParzenEstimator._LAZY_COEFFICIENTS and "_numerical" in self.__dict__:
+            self._precompute_logpdf_coefficients()
+            return self.__dict__[name]
+        raise AttributeError(name)
 
     def _precompute_logpdf_coefficients(self) -> None:
         """Expand -((x-mu)/sigma)^2/2 - log sigma - log Z into x^2*c1 + x*c2 + c3.

@@ -446,17 +446,20 @@ class TPESampler(BaseSampler):
 
         from optuna_amd.samplers._tpe import _device
 
-        above_sel = history.valid_rows(search_space, above_rows)
+        # One key hash of the space per suggest; everything below takes the cache.
+        cache = history.space_cache(search_space)
+        above_sel: np.ndarray | None = None
         if per_dim:
             # The batch is only equivalent to D independent 1-dim suggests
             # when every trial of both subsets defines every dim — then the
             # per-dim observation sets coincide with the joint ones.
-            below_sel_chk = history.valid_rows(search_space, below_rows)
+            above_sel = history.valid_rows(search_space, above_rows, cache)
+            below_sel_chk = history.valid_rows(search_space, below_rows, cache)
             if len(below_sel_chk) != len(below_rows) or len(above_sel) != len(
                 above_rows
             ):
                 return None
-        obs_below, orders_below = history.observations(search_space, below_rows)
+        obs_below, orders_below = history.observations(search_space, below_rows, cache)
 
         # Constant-liar rows: other workers' RUNNING trials join the "above"
         # set (params shared via system attrs). As an (L, D) matrix they ride
@@ -486,16 +489,38 @@ class TPESampler(BaseSampler):
                     liar_extras = np.asarray(rows_list, dtype=np.float64)
         n_liar = 0 if liar_extras is None else len(liar_extras)
 
+        # Fused device entry (see _device.fused_eligible): the above set is
+        # addressed as the complement of the short exclusion list, so its size
+        # follows from the valid-row counter in O(n_below) and the O(N) row
+        # selection is skipped.
+        n_below_valid = int(np.count_nonzero(cache.valid[below_rows]))
+        fused = _device.fused_eligible(
+            search_space,
+            per_dim=per_dim,
+            n_liar=n_liar,
+            default_estimator=self._parzen_estimator_cls is _ParzenEstimator,
+            rows_ascending=history._rows_number_ascending,
+            n_excl=len(below_rows) + cache.n_invalid,
+            n_below_kernels=n_below_valid + 1,
+        )
+        if fused:
+            n_above = cache.n_valid - n_below_valid
+        else:
+            if above_sel is None:
+                above_sel = history.valid_rows(search_space, above_rows, cache)
+            n_above = len(above_sel)
+
         use_device = (
             self._parzen_estimator_cls is _ParzenEstimator
             and _device.space_is_device_eligible(search_space)
-            and _device.device_ready(len(above_sel) + n_liar + 1)
+            and _device.device_ready(n_above + n_liar + 1)
         )
+        fused = fused and use_device
 
         obs_above: dict[str, np.ndarray] = {}
         orders_above: dict[str, np.ndarray] | None = None
         if not use_device:
-            obs_above, orders_above = history.observations(search_space, above_rows)
+            obs_above, orders_above = history.observations(search_space, above_rows, cache)
             if n_liar:
                 assert liar_extras is not None
                 obs_above = {
@@ -507,8 +532,15 @@ class TPESampler(BaseSampler):
         mpe_below = self._build_mpe(
             study, search_space, obs_below, handle_below=True, orders=orders_below
         )
+        x_below: np.ndarray | None = None
         if per_dim:
             samples_below = mpe_below.sample_per_dim(self._rng.rng, self._n_ei_candidates)
+        elif fused:
+            # Same draws as sample(); the fused entry takes the matrix as is.
+            x_below = mpe_below._sample_array(self._rng.rng, self._n_ei_candidates)
+            samples_below = {
+                name: x_below[:, i] for i, name in enumerate(mpe_below._param_names)
+            }
         else:
             samples_below = mpe_below.sample(self._rng.rng, self._n_ei_candidates)
 
@@ -517,10 +549,34 @@ class TPESampler(BaseSampler):
         # discrete cells, categorical); the small "below" estimator stays on
         # host (it also drives candidate sampling). The host path remains for
         # small histories and custom estimator classes.
-        if use_device:
+        if fused:
+            # One native call: fit, scoring, the below mixture and the EI
+            # difference all run on device; the below estimator above only
+            # drew the candidates (its scoring coefficients stay unbuilt).
+            assert x_below is not None
+            p = self._parzen_estimator_parameters
+            acq_func_vals = _device.score_above_resident(
+                cache,
+                None,
+                None if p.weights is default_weights else self._above_weights(n_above),
+                None,
+                p.consider_endpoints,
+                p.consider_magic_clip,
+                prior_weight=p.prior_weight,
+                fused=_device.FusedRequest(
+                    below_rows=below_rows,
+                    n_above=n_above,
+                    x_raw=x_below,
+                    below_mus=mpe_below._numerical.mus,
+                    below_sigmas=mpe_below._numerical.sigmas,
+                    below_weights=mpe_below.weights,
+                ),
+            )
+        elif use_device:
+            assert above_sel is not None
             weights_above = self._above_weights(len(above_sel) + n_liar)
             log_g = _device.score_above_resident(
-                history.space_cache(search_space),
+                cache,
                 above_sel,
                 weights_above,
                 samples_below,
@@ -536,7 +592,7 @@ class TPESampler(BaseSampler):
                 # score it against the resident table like the above set.
                 if len(below_sel_chk) >= 128:
                     log_l = _device.score_above_resident(
-                        history.space_cache(search_space),
+                        cache,
                         below_sel_chk,
                         mpe_below.weights,
                         samples_below,
