@@ -484,7 +484,7 @@ static void launch_mix_logpdf(hipStream_t st, const double* d_x,
                               const double* d_logw, const double* d_steps,
                               const double* d_nchoices, double cat_base,
                               int64_t K, int64_t D, int64_t S, double* d_out,
-                              double* d_scratch, bool merge = true) {
+                              double* d_scratch) {
     const int block = 256;
     const size_t shmem = (4 * (size_t)D + 2 * block) * sizeof(double);
     const int64_t n_chunks = mix_n_chunks(K);
@@ -500,8 +500,6 @@ static void launch_mix_logpdf(hipStream_t st, const double* d_x,
                        dim3(block), shmem, st, d_x, d_xedges, d_c1, d_c2, d_c3,
                        d_logw, d_steps, d_nchoices, cat_base, K, D, MIX_CHUNK,
                        d_part_m, d_part_s);
-    // merge == false: the caller merges the partials itself (fused suggest).
-    if (!merge) return;
     hipLaunchKernelGGL(k_mix_logpdf_merge, dim3((unsigned)S), dim3(64), 0, st,
                        d_part_m, d_part_s, n_chunks, S, d_out);
 }
@@ -1175,6 +1173,18 @@ __global__ void k_sorted_insert_by_value(int32_t* __restrict__ cols,  // (D, cap
 // sorted exclusion list (below rows + rows invalid for the space), so the
 // subset position of a member row is row - lower_bound(excl, row) and no
 // position map or compaction pass is needed.
+//
+// Three launches, split over two native calls so that only the last two sit
+// on the path the host waits for:
+//   k_fused_fit    above-set coefficients from the resident table and index.
+//                  Needs neither candidates nor the below estimator, so
+//                  fused_prepare launches it early, into a buffer the history
+//                  owns, and the host goes on building those meanwhile.
+//   k_fused_score  one block per 64-kernel slice of the above mixture plus one
+//                  per (narrower) slice of the below mixture, which fits its
+//                  own coefficients into LDS; (m, s) partials per slice.
+//   k_fused_merge  log-sum-exp of the above partials -> log g, of the below
+//                  partials -> log l; writes [log l - log g | log g | log l].
 // ---------------------------------------------------------------------------
 
 static constexpr int FUSED_MAX_EXCL = 1024;
@@ -1210,28 +1220,23 @@ __device__ inline void write_coeffs(double mu, double sigma, double low,
     }
 }
 
-// Grid (n_tiles + below_tiles, D). Blocks x < n_tiles fit one tile of 256
-// sorted positions of dim y straight from the resident sorted column; the
-// trailing blocks turn the uploaded below (mu, sigma) into coefficients.
+// Grid (n_tiles, D): each block fits one tile of 256 sorted positions of dim y
+// straight from the resident sorted column. It depends on nothing the
+// candidates or the below estimator supply, so fused_prepare can launch it
+// while the host is still building those.
 // domain = alow | ahigh | steps | n_choices (D each). logw == nullptr means
 // the caller uploaded custom log-weights; otherwise the dim-0 blocks write the
 // default ramp (numpy linspace arithmetic: k*step + start, uncontracted).
 __global__ void k_fused_fit(const double* __restrict__ params,
                             const int32_t* __restrict__ sorted,  // (D, s_stride)
-                            int64_t s_stride, int64_t Nv, int64_t n_tiles,
+                            int64_t s_stride, int64_t Nv,
                             const int32_t* __restrict__ excl, int E,
                             const double* __restrict__ domain, int64_t Na,
                             int64_t D, int consider_endpoints, int magic_clip,
                             double* __restrict__ c1, double* __restrict__ c2,
                             double* __restrict__ c3, double* __restrict__ logw,
                             int64_t w_num, double w_start, double w_step,
-                            double log_total, double prior_weight,
-                            const double* __restrict__ bmu,   // (Kb, D)
-                            const double* __restrict__ bsig,  // (Kb, D)
-                            const double* __restrict__ bw,    // (Kb,)
-                            int64_t Kb, double* __restrict__ bc1,
-                            double* __restrict__ bc2, double* __restrict__ bc3,
-                            double* __restrict__ blogw) {
+                            double log_total, double prior_weight) {
     __shared__ int32_t s_excl[FUSED_MAX_EXCL];
     __shared__ int s_prev[FUSED_TILE];
     __shared__ int s_next[FUSED_TILE];
@@ -1243,17 +1248,6 @@ __global__ void k_fused_fit(const double* __restrict__ params,
     const bool stepped = domain[2 * D + d] > 0.0;
     const double range = high - low;
     const int i = threadIdx.x;
-
-    if ((int64_t)blockIdx.x >= n_tiles) {
-        // Below estimator: same coefficient formulas, (D, Kb) k-major.
-        const int64_t kb = ((int64_t)blockIdx.x - n_tiles) * FUSED_TILE + i;
-        if (kb < Kb) {
-            write_coeffs(bmu[kb * D + d], bsig[kb * D + d], low, high, stepped,
-                         bc1, bc2, bc3, d * Kb + kb);
-            if (d == 0) blogw[kb] = log(bw[kb]);
-        }
-        return;
-    }
 
     for (int e = i; e < E; e += FUSED_TILE) s_excl[e] = excl[e];
     __syncthreads();
@@ -1352,104 +1346,244 @@ __global__ void k_fused_fit(const double* __restrict__ params,
     }
 }
 
-// Block-wide merge of per-thread online-logsumexp states; the result lands
-// in red_m[0] / red_s[0]. blockDim.x must be a power of two.
-__device__ inline void block_lse_merge(double* red_m, double* red_s, double m,
-                                       double acc) {
-    red_m[threadIdx.x] = m;
-    red_s[threadIdx.x] = acc;
-    __syncthreads();
-    for (int stride = blockDim.x / 2; stride > 0; stride >>= 1) {
-        if (threadIdx.x < stride) {
-            double m2 = red_m[threadIdx.x + stride];
-            double s2 = red_s[threadIdx.x + stride];
-            double m1 = red_m[threadIdx.x];
-            double s1 = red_s[threadIdx.x];
-            if (m2 > m1) {
-                s1 = s1 * exp(m1 - m2) + s2;
-                m1 = m2;
-            } else if (m1 != -INFINITY) {
-                s1 = s1 + s2 * exp(m2 - m1);
-            }
-            red_m[threadIdx.x] = m1;
-            red_s[threadIdx.x] = s1;
+// ---------------------------------------------------------------------------
+// Fused scoring: the above mixture and the below mixture in one launch.
+//
+// A block owns a slice of SCORE_SLICE mixture kernels (one per lane) and up to
+// SCORE_CAND candidates (SCORE_SG per wavefront), so a coefficient is fetched
+// once per block instead of once per candidate. Blocks x < n_above_slices
+// score slices of the above mixture from the fitted (D, K) coefficients; the
+// trailing blocks are the below mixture: they turn their slice (below_slice
+// kernels, at most SCORE_SLICE) of the uploaded (mu, sigma) into coefficients
+// in LDS (same formulas as the fit) and score it the same way. Every wavefront reduces its own candidates across its 64
+// lanes (maximum first, then one exp per term and a plain sum) and writes one
+// (m, s) partial per (slice, candidate); k_fused_merge finishes the job.
+// Dims are walked in passes of SCORE_DC so the LDS footprint does not depend
+// on D; blockIdx.y walks candidate groups of SCORE_CAND.
+// ---------------------------------------------------------------------------
+
+static constexpr int SCORE_SLICE = 64;
+static constexpr int SCORE_WAVES = 4;
+static constexpr int SCORE_SG = 6;
+static constexpr int SCORE_CAND = SCORE_WAVES * SCORE_SG;
+static constexpr int SCORE_DC = 24;
+
+__device__ inline double wave_max(double v) {
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+
+__device__ inline double wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// All-continuous pass: the lane's 3 * SCORE_DC coefficients are loaded back to
+// back into registers (rows past dn repeat the last one, so there is no branch
+// between the loads), then every candidate of the wavefront takes its two FMAs.
+__device__ __forceinline__ void score_pass_cont(const double* q1, const double* q2,
+                                                const double* q3, int64_t stride,
+                                                int dn, const double* sx,
+                                                const double* sx2,
+                                                double (&acc)[SCORE_SG]) {
+    double r1[SCORE_DC], r2[SCORE_DC], r3[SCORE_DC];
+    int64_t o = 0;
+#pragma unroll
+    for (int d = 0; d < SCORE_DC; ++d) {
+        r1[d] = q1[o];
+        r2[d] = q2[o];
+        r3[d] = q3[o];
+        o += (d + 1 < dn) ? stride : 0;
+    }
+#pragma unroll
+    for (int d = 0; d < SCORE_DC; ++d) {
+        if (d < dn) {
+#pragma unroll
+            for (int j = 0; j < SCORE_SG; ++j)
+                acc[j] += sx2[j * SCORE_DC + d] * r1[d] + sx[j * SCORE_DC + d] * r2[d] +
+                          r3[d];
         }
-        __syncthreads();
     }
 }
 
-// Merge stage of the fused suggest, one block per candidate: merges the above
-// partials into log g (n_chunks == 0: log g was already written to logg_in by
-// the single-phase kernel), evaluates the below mixture's logsumexp over its
-// <= 1024 kernels, and writes out = [log l - log g | log g | log l] (3, S).
-__global__ void k_mix_merge_ei(const double* __restrict__ part_m,
-                               const double* __restrict__ part_s,
-                               int64_t n_chunks, int64_t S,
-                               const double* __restrict__ logg_in,
-                               const double* __restrict__ x,       // (S, D)
-                               const double* __restrict__ xedges,  // (S, 2D)
-                               const double* __restrict__ bc1,
-                               const double* __restrict__ bc2,
-                               const double* __restrict__ bc3,
-                               const double* __restrict__ blogw,
-                               const double* __restrict__ steps,
-                               const double* __restrict__ n_choices,
-                               int64_t Kb, int64_t D,
-                               double* __restrict__ out) {
-    extern __shared__ double lds[];
-    double* xs = lds;
-    double* x2 = lds + D;
-    double* xl = lds + 2 * D;
-    double* xr = lds + 3 * D;
-    double* red_m = lds + 4 * D;
-    double* red_s = red_m + blockDim.x;
+// Pass with stepped dims: those integrate the step cell against (mu, sigma)
+// with the cached -logZ; the others keep the quadratic form.
+__device__ inline void score_pass_stepped(const double* q1, const double* q2,
+                                          const double* q3, int64_t stride, int dn,
+                                          const double* __restrict__ steps,  // or null
+                                          const double* sx, const double* sx2,
+                                          const double* sxl, const double* sxr,
+                                          double (&acc)[SCORE_SG]) {
+#pragma nounroll
+    for (int d = 0; d < dn; ++d) {
+        const double a = q1[d * stride];
+        const double b = q2[d * stride];
+        const double c = q3[d * stride];
+        if (steps && steps[d] > 0.0) {
+            // One copy of the cell integral's code, not SCORE_SG of them.
+            // The loop is kept rolled; acc is rotated through slot 0 so its
+            // indices stay static (registers) and SCORE_SG turns restore it.
+#pragma nounroll
+            for (int j = 0; j < SCORE_SG; ++j) {
+                const double t =
+                    acc[0] + (tn::log_gauss_mass((sxl[j * SCORE_DC + d] - a) / b,
+                                                 (sxr[j * SCORE_DC + d] - a) / b) +
+                              c);
+#pragma unroll
+                for (int i = 0; i + 1 < SCORE_SG; ++i) acc[i] = acc[i + 1];
+                acc[SCORE_SG - 1] = t;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < SCORE_SG; ++j)
+                acc[j] += sx2[j * SCORE_DC + d] * a + sx[j * SCORE_DC + d] * b + c;
+        }
+    }
+}
 
-    const int64_t s = blockIdx.x;
-    for (int64_t d = threadIdx.x; d < D; d += blockDim.x) {
-        const double v = x[s * D + d];
-        xs[d] = v;
-        x2[d] = v * v;
-        xl[d] = xedges[s * 2 * D + d];
-        xr[d] = xedges[s * 2 * D + D + d];
+__global__ __launch_bounds__(SCORE_SLICE * SCORE_WAVES)
+void k_fused_score(const double* __restrict__ x,       // (S, D)
+                   const double* __restrict__ xedges,  // (S, 2D), read if any_stepped
+                   const double* __restrict__ c1,      // (D, K) above coefficients
+                   const double* __restrict__ c2,
+                   const double* __restrict__ c3,
+                   const double* __restrict__ logw,    // (K,)
+                   int64_t K, int64_t n_above_slices,
+                   const double* __restrict__ bmu,     // (Kb, D)
+                   const double* __restrict__ bsig,    // (Kb, D)
+                   const double* __restrict__ bw,      // (Kb,)
+                   int64_t Kb, int below_slice,
+                   const double* __restrict__ domain, int any_stepped,
+                   int64_t D, int64_t S,
+                   double* __restrict__ part_m,    // (slices, S)
+                   double* __restrict__ part_s) {  // (slices, S)
+    __shared__ double s_x[SCORE_CAND * SCORE_DC];
+    __shared__ double s_x2[SCORE_CAND * SCORE_DC];
+    __shared__ double s_xl[SCORE_CAND * SCORE_DC];
+    __shared__ double s_xr[SCORE_CAND * SCORE_DC];
+    __shared__ double s_bc[3 * SCORE_DC * SCORE_SLICE];  // below blocks only
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int64_t slot = blockIdx.x;
+    const bool below = slot >= n_above_slices;
+    const int64_t Kmix = below ? Kb : K;
+    // Below slices are narrower (see fused_score): building a coefficient
+    // costs far more than using it, so they are cut to one per thread.
+    const int slice = below ? below_slice : SCORE_SLICE;
+    const int64_t k0 = (below ? slot - n_above_slices : slot) * slice;
+    const int kn = (int)(Kmix - k0 < slice ? Kmix - k0 : slice);
+    const bool active = lane < kn;
+    // Idle lanes read their slice's last kernel, so every load is in bounds;
+    // their terms are dropped before the reduction.
+    const int lc = active ? lane : kn - 1;
+    const int64_t s0 = (int64_t)blockIdx.y * SCORE_CAND;
+    const int64_t sw = s0 + (int64_t)wave * SCORE_SG;
+    const bool wave_busy = sw < S;  // wavefront-uniform
+
+    double acc[SCORE_SG];
+    {
+        const double lw = below ? log(bw[k0 + lc]) : logw[k0 + lc];
+#pragma unroll
+        for (int j = 0; j < SCORE_SG; ++j) acc[j] = lw;
     }
 
-    double log_g;
-    if (n_chunks > 0) {
-        double m = -INFINITY, acc = 0.0;
-        for (int64_t c = threadIdx.x; c < n_chunks; c += blockDim.x) {
-            const double m2 = part_m[c * S + s];
-            const double s2 = part_s[c * S + s];
-            if (m2 > m) {
-                acc = acc * exp(m - m2) + s2;
-                m = m2;
-            } else if (m != -INFINITY) {
-                acc += s2 * exp(m2 - m);
+    for (int64_t d0 = 0; d0 < D; d0 += SCORE_DC) {
+        const int dn = (int)(D - d0 < SCORE_DC ? D - d0 : SCORE_DC);
+        if (d0 > 0) __syncthreads();  // the previous pass has read its LDS
+        // Candidates past S repeat the last one; nothing is written for them.
+        for (int p = threadIdx.x; p < SCORE_CAND * dn; p += blockDim.x) {
+            const int c = p / dn;
+            const int dl = p - c * dn;
+            const int64_t s = s0 + c < S ? s0 + c : S - 1;
+            const double v = x[s * D + d0 + dl];
+            s_x[c * SCORE_DC + dl] = v;
+            s_x2[c * SCORE_DC + dl] = v * v;
+            if (any_stepped) {
+                s_xl[c * SCORE_DC + dl] = xedges[s * 2 * D + d0 + dl];
+                s_xr[c * SCORE_DC + dl] = xedges[s * 2 * D + D + d0 + dl];
             }
         }
-        block_lse_merge(red_m, red_s, m, acc);
-        log_g = (red_m[0] == -INFINITY) ? -INFINITY : red_m[0] + log(red_s[0]);
-    } else {
-        log_g = logg_in[s];
-    }
-    __syncthreads();  // xs staged; red_* free for reuse
-
-    double m = -INFINITY, acc = 0.0;
-    for (int64_t k = threadIdx.x; k < Kb; k += blockDim.x) {
-        double t = blogw[k];
-        for (int64_t d = 0; d < D; ++d)
-            t += mix_term(bc1, bc2, bc3, steps, n_choices, 0.0, xs, x2, xl, xr,
-                          Kb, k, d);
-        if (t > m) {
-            acc = acc * exp(m - t) + 1.0;
-            m = t;
-        } else if (m != -INFINITY) {
-            acc += exp(t - m);
+        if (below) {
+            for (int p = threadIdx.x; p < kn * dn; p += blockDim.x) {
+                const int kl = p / dn;
+                const int dl = p - kl * dn;
+                const int64_t d = d0 + dl;
+                write_coeffs(bmu[(k0 + kl) * D + d], bsig[(k0 + kl) * D + d],
+                             domain[d], domain[D + d], domain[2 * D + d] > 0.0,
+                             s_bc, s_bc + SCORE_DC * SCORE_SLICE,
+                             s_bc + 2 * SCORE_DC * SCORE_SLICE,
+                             dl * SCORE_SLICE + kl);
+            }
+        }
+        __syncthreads();
+        if (!wave_busy) continue;
+        const int co = wave * SCORE_SG * SCORE_DC;
+        if (below) {
+            // Coefficients sit in LDS: the plain per-dim loop has no global
+            // latency to hide (s_xl / s_xr are only read for stepped dims).
+            const double* q = s_bc + lc;
+            score_pass_stepped(q, q + SCORE_DC * SCORE_SLICE,
+                               q + 2 * SCORE_DC * SCORE_SLICE, SCORE_SLICE, dn,
+                               any_stepped ? domain + 2 * D + d0 : nullptr,
+                               s_x + co, s_x2 + co, s_xl + co, s_xr + co, acc);
+        } else {
+            // k-major (D, K): lanes of a wavefront read consecutive k.
+            const int64_t o = d0 * K + k0 + lc;
+            if (any_stepped)
+                score_pass_stepped(c1 + o, c2 + o, c3 + o, K, dn,
+                                   domain + 2 * D + d0, s_x + co, s_x2 + co,
+                                   s_xl + co, s_xr + co, acc);
+            else
+                score_pass_cont(c1 + o, c2 + o, c3 + o, K, dn, s_x + co,
+                                s_x2 + co, acc);
         }
     }
-    block_lse_merge(red_m, red_s, m, acc);
-    if (threadIdx.x == 0) {
-        const double log_l =
-            (red_m[0] == -INFINITY) ? -INFINITY : red_m[0] + log(red_s[0]);
+    if (!wave_busy) return;
+
+    // A slice whose terms are all -inf (zero weights) yields (-inf, 0), never
+    // NaN: exp(-inf - -inf) is not evaluated.
+#pragma unroll
+    for (int j = 0; j < SCORE_SG; ++j) {
+        const double t = active ? acc[j] : -INFINITY;
+        const double M = wave_max(t);
+        const double e = (M == -INFINITY) ? 0.0 : exp(t - M);
+        const double sum = wave_sum(e);
+        if (lane == 0 && sw + j < S) {
+            part_m[slot * S + sw + j] = M;
+            part_s[slot * S + sw + j] = sum;
+        }
+    }
+}
+
+// Log-sum-exp of n (m, s) partials, S apart, by one wavefront.
+__device__ inline double wave_lse_partials(const double* __restrict__ pm,
+                                           const double* __restrict__ ps,
+                                           int64_t n, int64_t S, int lane) {
+    double m = -INFINITY;
+    for (int64_t c = lane; c < n; c += 64) m = fmax(m, pm[c * S]);
+    const double M = wave_max(m);
+    if (M == -INFINITY) return -INFINITY;
+    double acc = 0.0;
+    for (int64_t c = lane; c < n; c += 64) acc += ps[c * S] * exp(pm[c * S] - M);
+    return M + log(wave_sum(acc));
+}
+
+// Merge stage of the fused suggest, one wavefront per candidate: the above
+// partials give log g, the below partials log l;
+// out = [log l - log g | log g | log l] (3, S).
+__global__ void k_fused_merge(const double* __restrict__ part_m,
+                              const double* __restrict__ part_s,
+                              int64_t n_above_slices, int64_t n_below_slices,
+                              int64_t S, double* __restrict__ out) {
+    const int64_t s = blockIdx.x;
+    const int lane = threadIdx.x;
+    const double log_g =
+        wave_lse_partials(part_m + s, part_s + s, n_above_slices, S, lane);
+    const double log_l = wave_lse_partials(part_m + n_above_slices * S + s,
+                                           part_s + n_above_slices * S + s,
+                                           n_below_slices, S, lane);
+    if (lane == 0) {
         out[s] = log_l - log_g;
         out[S + s] = log_g;
         out[2 * S + s] = log_l;
@@ -1466,6 +1600,7 @@ class TpeDeviceHistory {
         if (params_) (void)hipFree(params_);
         if (sorted_) (void)hipFree(sorted_);
         if (domain_) (void)hipFree(domain_);
+        if (coef_) (void)hipFree(coef_);
     }
 
     int64_t n_rows() const { return n_; }
@@ -1475,6 +1610,7 @@ class TpeDeviceHistory {
             throw std::runtime_error("append: block must be (n_new, D)");
         const int64_t n_new = block.shape(0);
         if (n_new == 0) return;
+        prep_.valid = false;
         hipStream_t st = g_ws.get_stream();
         if (n_ + n_new > capacity_) {
             int64_t new_cap = std::max<int64_t>(1024, (n_ + n_new) * 2);
@@ -1664,6 +1800,7 @@ class TpeDeviceHistory {
         const int64_t Nv = cols.empty() ? 0 : (int64_t)cols[0].size();
         if ((int64_t)cols.size() != D_ && Nv > 0)
             throw std::runtime_error("upload_sorted: wrong number of columns");
+        prep_.valid = false;
         hipStream_t st = g_ws.get_stream();
         ensure_sorted_capacity(Nv, st);
         g_ws.begin_uploads();
@@ -1680,6 +1817,7 @@ class TpeDeviceHistory {
         if (!sorted_valid_) throw std::runtime_error("insert_sorted before upload");
         const int64_t n_new = pos.ndim() == 2 ? pos.shape(0) : 0;
         if (n_new == 0) return;
+        prep_.valid = false;
         if (pos.shape(1) != D_ || rows.shape(0) != n_new || rows.shape(1) != D_)
             throw std::runtime_error("insert_sorted: shape mismatch");
         hipStream_t st = g_ws.get_stream();
@@ -1711,6 +1849,7 @@ class TpeDeviceHistory {
         if (!sorted_valid_)
             throw std::runtime_error("insert_sorted_by_value before upload");
         if (n_new <= 0) return;
+        prep_.valid = false;
         if (first_row < 0 || first_row + n_new > n_)
             throw std::runtime_error("insert_sorted_by_value: rows not in table");
         hipStream_t st = g_ws.get_stream();
@@ -1743,6 +1882,7 @@ class TpeDeviceHistory {
         if ((int64_t)alow.size() != D_ || (int64_t)ahigh.size() != D_ ||
             (int64_t)steps.size() != D_ || (int64_t)n_choices.size() != D_)
             throw std::runtime_error("set_domain: shape mismatch");
+        prep_.valid = false;
         std::vector<double> host(4 * (size_t)D_);
         std::copy(alow.data(), alow.data() + D_, host.begin());
         std::copy(ahigh.data(), ahigh.data() + D_, host.begin() + D_);
@@ -1762,8 +1902,15 @@ class TpeDeviceHistory {
         }
     }
 
-    // Fused suggest: one packed upload, fit + below coefficients in one
-    // launch, scoring, and below log-pdf / EI in the merge stage.
+    // Fused suggest, in two native calls that share one stream:
+    //   fused_prepare  uploads the exclusion list (and custom log-weights) and
+    //                  launches the above-set fit into this history's own
+    //                  coefficient buffer; returns without synchronising.
+    //   fused_score    one packed upload (candidates + below estimator),
+    //                  k_fused_score, k_fused_merge (which writes the result
+    //                  into pinned host memory: no download). It reuses
+    //                  the prepared fit when that is still valid for its
+    //                  arguments and otherwise runs the fit itself first.
     //   excl     sorted table rows NOT in the above set (below + invalid rows)
     //   n_above  size of the above set (= resident index rows not in excl)
     //   x/xedges candidates (KDE domain); xedges only read for stepped dims
@@ -1771,7 +1918,19 @@ class TpeDeviceHistory {
     //   logw     custom above log-weights (n_above + 1,), or empty for the
     //            default ramp, which the device writes itself from
     //            (w_num, w_start, w_step, log_total)
-    // Returns (S,) log l - log g.
+    void fused_prepare(const arr_i32& excl, int64_t n_above, const arr_f64& logw,
+                       int64_t w_num, double w_start, double w_step,
+                       double log_total, double prior_weight,
+                       bool consider_endpoints, bool magic_clip) {
+        check_fit_args("fused_prepare", excl, n_above, logw);
+        g_ws.begin_uploads();
+        launch_fit(excl, n_above, logw, w_num, w_start, w_step, log_total,
+                   prior_weight, consider_endpoints, magic_clip,
+                   /*guard_staging=*/true);
+    }
+
+    // Returns (S,) log l - log g, or with return_parts the test/debug form
+    // ((3, S) [ei | log g | log l], (K,) above logw).
     py::object fused_score(const arr_i32& excl, int64_t n_above,
                                     const arr_f64& x, const arr_f64& xedges,
                                     const arr_f64& bmu, const arr_f64& bsig,
@@ -1781,69 +1940,48 @@ class TpeDeviceHistory {
                                     double prior_weight,
                                     bool consider_endpoints, bool magic_clip,
                                     bool return_parts) {
-        if (!sorted_valid_) throw std::runtime_error("fused_score before upload_sorted");
-        if (!domain_) throw std::runtime_error("fused_score before set_domain");
-        if (has_categorical_)
-            throw std::runtime_error("fused_score: categorical dims unsupported");
+        check_fit_args("fused_score", excl, n_above, logw);
         if (x.ndim() != 2 || x.shape(1) != D_ || bmu.ndim() != 2 ||
             bmu.shape(1) != D_ || bsig.ndim() != 2 || bsig.shape(1) != D_)
             throw std::runtime_error("fused_score: shape mismatch");
         const int64_t S = x.shape(0);
         const int64_t Kb = bmu.shape(0);
-        const int64_t E = excl.size();
-        const int64_t Na = n_above;
-        const int64_t K = Na + 1;
-        const int64_t Nv = n_sorted_;
-        const bool custom_w = logw.size() > 0;
+        const int64_t K = n_above + 1;
         if (S < 1 || Kb < 1 || Kb > FUSED_MAX_BELOW || bsig.shape(0) != Kb ||
-            (int64_t)bw.size() != Kb || E > FUSED_MAX_EXCL || Na < 0 ||
-            Na > Nv || Na + E < Nv || (custom_w && (int64_t)logw.size() != K) ||
+            (int64_t)bw.size() != Kb ||
             (has_steps_ && (int64_t)xedges.size() != 2 * S * D_))
             throw std::runtime_error("fused_score: shape mismatch");
-        // Strictly ascending in-table rows: keeps row - lower_bound(excl, row)
-        // inside [0, n_above) for every member row.
-        const int32_t* ex = excl.data();
-        for (int64_t e = 0; e < E; ++e)
-            if (ex[e] < 0 || ex[e] >= n_ || (e > 0 && ex[e] <= ex[e - 1]))
-                throw std::runtime_error("fused_score: excl must be sorted table rows");
 
         hipStream_t st = g_ws.get_stream();
+        g_ws.begin_uploads();
+        if (!prepared_matches(excl, n_above, logw, w_num, w_start, w_step,
+                              log_total, prior_weight, consider_endpoints,
+                              magic_clip))
+            launch_fit(excl, n_above, logw, w_num, w_start, w_step, log_total,
+                       prior_weight, consider_endpoints, magic_clip,
+                       /*guard_staging=*/false);
+
         // Packed region (one pinned slice, one DMA, same layout on device):
-        //   x | bmu | bsig | bw | [logw] | excl (i32, padded) | [xedges]
-        // The xedges slot is always reserved on device (the scoring kernels
-        // stage it unconditionally) but only uploaded when a dim is stepped.
+        //   x | bmu | bsig | bw | [xedges]
         const size_t n_x = (size_t)S * D_;
         const size_t n_b = (size_t)Kb * D_;
-        const size_t n_excl = ((size_t)E + 1) / 2;
-        const size_t n_logw_up = custom_w ? (size_t)K : 0;
-        const size_t up_doubles =
-            n_x + 2 * n_b + Kb + n_logw_up + n_excl + (has_steps_ ? 2 * n_x : 0);
-        const size_t packed_doubles = n_x + 2 * n_b + Kb + n_logw_up + n_excl + 2 * n_x;
-        const size_t n_c = (size_t)K * D_;
-        const int64_t n_chunks = mix_n_chunks(K);
-        const size_t n_scratch = 2 * (size_t)n_chunks * S;
-        double* base = g_ws.ensure(packed_doubles + 3 * n_c + K + 3 * n_b + Kb +
-                                   n_scratch + 4 * (size_t)S + 16);
+        const size_t up_doubles = n_x + 2 * n_b + Kb + (has_steps_ ? 2 * n_x : 0);
+        const int64_t n_as = (K + SCORE_SLICE - 1) / SCORE_SLICE;
+        // Below slices: as many kernels as give each of the block's threads
+        // at most one (kernel, dim) coefficient to build per pass over dims.
+        const int64_t pass_dims = std::min<int64_t>(D_, SCORE_DC);
+        const int below_slice = (int)std::max<int64_t>(
+            1, std::min<int64_t>(SCORE_SLICE, SCORE_SLICE * SCORE_WAVES / pass_dims));
+        const int64_t n_bs = (Kb + below_slice - 1) / below_slice;
+        const size_t n_part = (size_t)(n_as + n_bs) * S;
+        double* base = g_ws.ensure(up_doubles + 2 * n_part + 16);
         double* d_x = base;
         double* d_bmu = d_x + n_x;
         double* d_bsig = d_bmu + n_b;
         double* d_bw = d_bsig + n_b;
-        double* d_logw_up = d_bw + Kb;
-        int32_t* d_excl = reinterpret_cast<int32_t*>(d_logw_up + n_logw_up);
-        double* d_xedges = d_logw_up + n_logw_up + n_excl;
-        double* d_c1 = base + packed_doubles;
-        double* d_c2 = d_c1 + n_c;
-        double* d_c3 = d_c2 + n_c;
-        double* d_logw = d_c3 + n_c;
-        double* d_bc1 = d_logw + K;
-        double* d_bc2 = d_bc1 + n_b;
-        double* d_bc3 = d_bc2 + n_b;
-        double* d_blogw = d_bc3 + n_b;
-        double* d_scratch = d_blogw + Kb;
-        double* d_logg = d_scratch + n_scratch;
-        double* d_out = d_logg + S;
-
-        g_ws.begin_uploads();
+        double* d_xedges = d_bw + Kb;
+        double* d_part_m = base + up_doubles;
+        double* d_part_s = d_part_m + n_part;
         {
             double* h = reinterpret_cast<double*>(g_ws.stage(up_doubles * 8, st));
             double* p = h;
@@ -1851,64 +1989,166 @@ class TpeDeviceHistory {
             memcpy(p, bmu.data(), n_b * 8); p += n_b;
             memcpy(p, bsig.data(), n_b * 8); p += n_b;
             memcpy(p, bw.data(), (size_t)Kb * 8); p += Kb;
-            if (custom_w) { memcpy(p, logw.data(), (size_t)K * 8); p += K; }
-            if (n_excl) {
-                p[n_excl - 1] = 0.0;  // defined padding for odd E
-                memcpy(p, ex, (size_t)E * 4);
-                p += n_excl;
-            }
             if (has_steps_) memcpy(p, xedges.data(), 2 * n_x * 8);
             HIP_CHECK(hipMemcpyAsync(base, h, up_doubles * 8,
                                      hipMemcpyHostToDevice, st));
         }
 
-        const double* d_steps = domain_ + 2 * D_;
-        const double* d_nchoices = domain_ + 3 * D_;
-        const int64_t n_tiles = std::max<int64_t>(1, (Nv + FUSED_TILE - 1) / FUSED_TILE);
-        const int64_t b_tiles = (Kb + FUSED_TILE - 1) / FUSED_TILE;
-        hipLaunchKernelGGL(k_fused_fit,
-                           dim3((unsigned)(n_tiles + b_tiles), (unsigned)D_),
-                           dim3(FUSED_TILE), 0, st, params_, sorted_, sorted_cap_,
-                           Nv, n_tiles, d_excl, (int)E, domain_, Na, D_,
-                           consider_endpoints ? 1 : 0, magic_clip ? 1 : 0, d_c1,
-                           d_c2, d_c3, custom_w ? nullptr : d_logw, w_num,
-                           w_start, w_step, log_total, prior_weight, d_bmu,
-                           d_bsig, d_bw, Kb, d_bc1, d_bc2, d_bc3, d_blogw);
-        const double* d_logw_use = custom_w ? d_logw_up : d_logw;
-        const double cat_base = prior_weight / (double)K;
-        launch_mix_logpdf(st, d_x, d_xedges, d_c1, d_c2, d_c3, d_logw_use,
-                          d_steps, d_nchoices, cat_base, K, D_, S, d_logg,
-                          d_scratch, /*merge=*/false);
-        {
-            const int block = 256;
-            const size_t shmem = (4 * (size_t)D_ + 2 * block) * sizeof(double);
-            hipLaunchKernelGGL(k_mix_merge_ei, dim3((unsigned)S), dim3(block),
-                               shmem, st, d_scratch, d_scratch + (size_t)n_chunks * S,
-                               n_chunks > 1 ? n_chunks : 0, S, d_logg, d_x,
-                               d_xedges, d_bc1, d_bc2, d_bc3, d_blogw, d_steps,
-                               d_nchoices, Kb, D_, d_out);
-        }
+        const size_t n_c = (size_t)K * D_;
+        const double* d_logw = coef_ + 3 * n_c;
+        const int64_t n_groups = (S + SCORE_CAND - 1) / SCORE_CAND;
+        hipLaunchKernelGGL(k_fused_score,
+                           dim3((unsigned)(n_as + n_bs), (unsigned)n_groups),
+                           dim3(SCORE_SLICE * SCORE_WAVES), 0, st, d_x, d_xedges,
+                           coef_, coef_ + n_c, coef_ + 2 * n_c, d_logw, K, n_as,
+                           d_bmu, d_bsig, d_bw, Kb, below_slice, domain_,
+                           has_steps_ ? 1 : 0,
+                           D_, S, d_part_m, d_part_s);
+        // The merge writes its (3, S) result straight into a pinned host slot
+        // (kernels can address hipHostMalloc memory), which saves the
+        // download's own dispatch on the serial chain. The slot belongs to
+        // this upload batch and is read after the stream sync below, so it is
+        // not reused before the kernel has finished.
+        const double* h_out =
+            reinterpret_cast<const double*>(g_ws.stage(3 * (size_t)S * 8, st));
+        hipLaunchKernelGGL(k_fused_merge, dim3((unsigned)S), dim3(64), 0, st,
+                           d_part_m, d_part_s, n_as, n_bs, S,
+                           const_cast<double*>(h_out));
         if (return_parts) {
-            // Test/debug form: ((3, S) [ei | log g | log l], (K,) above logw).
             py::array_t<double> parts({(int64_t)3, S});
             py::array_t<double> lw(K);
-            HIP_CHECK(hipMemcpyAsync(parts.mutable_data(), d_out, 3 * (size_t)S * 8,
-                                     hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipMemcpyAsync(lw.mutable_data(), d_logw_use, (size_t)K * 8,
+            HIP_CHECK(hipMemcpyAsync(lw.mutable_data(), d_logw, (size_t)K * 8,
                                      hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
             HIP_CHECK(hipGetLastError());
+            memcpy(parts.mutable_data(), h_out, 3 * (size_t)S * 8);
             return py::make_tuple(parts, lw);
         }
         py::array_t<double> out(S);
-        HIP_CHECK(hipMemcpyAsync(out.mutable_data(), d_out, (size_t)S * 8,
-                                 hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipGetLastError());
+        memcpy(out.mutable_data(), h_out, (size_t)S * 8);
         return out;
     }
 
   private:
+    // What the coefficients in coef_ were fitted from. They stay usable only
+    // while the table, the index, the domain and every fit argument are the
+    // same; every mutator of those clears `valid`.
+    struct PreparedFit {
+        bool valid = false;
+        int64_t n = 0, n_sorted = 0, Na = 0, w_num = 0;
+        double w_start = 0.0, w_step = 0.0, log_total = 0.0, prior_weight = 0.0;
+        bool consider_endpoints = false, magic_clip = false;
+        std::vector<int32_t> excl;
+        std::vector<double> logw;  // custom log-weights, empty for the ramp
+    };
+
+    void check_fit_args(const char* who, const arr_i32& excl, int64_t Na,
+                        const arr_f64& logw) const {
+        const std::string w(who);
+        if (!sorted_valid_) throw std::runtime_error(w + " before upload_sorted");
+        if (!domain_) throw std::runtime_error(w + " before set_domain");
+        if (has_categorical_)
+            throw std::runtime_error(w + ": categorical dims unsupported");
+        const int64_t E = excl.size();
+        const int64_t Nv = n_sorted_;
+        if (E > FUSED_MAX_EXCL || Na < 0 || Na > Nv || Na + E < Nv ||
+            (logw.size() > 0 && (int64_t)logw.size() != Na + 1))
+            throw std::runtime_error(w + ": shape mismatch");
+        // Strictly ascending in-table rows: keeps row - lower_bound(excl, row)
+        // inside [0, n_above) for every member row.
+        const int32_t* ex = excl.data();
+        for (int64_t e = 0; e < E; ++e)
+            if (ex[e] < 0 || ex[e] >= n_ || (e > 0 && ex[e] <= ex[e - 1]))
+                throw std::runtime_error(w + ": excl must be sorted table rows");
+    }
+
+    // Bit-wise comparisons throughout: equal arguments give the same fit.
+    bool prepared_matches(const arr_i32& excl, int64_t Na, const arr_f64& logw,
+                          int64_t w_num, double w_start, double w_step,
+                          double log_total, double prior_weight,
+                          bool consider_endpoints, bool magic_clip) const {
+        const PreparedFit& p = prep_;
+        const double a[4] = {w_start, w_step, log_total, prior_weight};
+        const double b[4] = {p.w_start, p.w_step, p.log_total, p.prior_weight};
+        return p.valid && p.n == n_ && p.n_sorted == n_sorted_ && p.Na == Na &&
+               p.w_num == w_num && memcmp(a, b, sizeof(a)) == 0 &&
+               p.consider_endpoints == consider_endpoints &&
+               p.magic_clip == magic_clip &&
+               p.excl.size() == (size_t)excl.size() &&
+               (p.excl.empty() ||
+                memcmp(p.excl.data(), excl.data(), p.excl.size() * 4) == 0) &&
+               p.logw.size() == (size_t)logw.size() &&
+               (p.logw.empty() ||
+                memcmp(p.logw.data(), logw.data(), p.logw.size() * 8) == 0);
+    }
+
+    // Upload [logw] | excl into coef_ and launch the fit behind it. The caller
+    // has opened the upload batch; with guard_staging the batch is closed with
+    // the event guard right behind the DMA (the caller does not synchronise).
+    // coef_ = c1 | c2 | c3 (D, K each, k-major) | logw (K) | excl (i32, padded).
+    void launch_fit(const arr_i32& excl, int64_t Na, const arr_f64& logw,
+                    int64_t w_num, double w_start, double w_step,
+                    double log_total, double prior_weight,
+                    bool consider_endpoints, bool magic_clip, bool guard_staging) {
+        prep_.valid = false;
+        hipStream_t st = g_ws.get_stream();
+        const int64_t E = excl.size();
+        const int64_t K = Na + 1;
+        const int64_t Nv = n_sorted_;
+        const bool custom_w = logw.size() > 0;
+        const size_t n_c = (size_t)K * D_;
+        const size_t n_excl = ((size_t)E + 1) / 2;
+        const size_t need = 3 * n_c + K + n_excl;
+        if (need > coef_cap_) {
+            // hipFree waits for the launches that still read the old buffer.
+            if (coef_) HIP_CHECK(hipFree(coef_));
+            coef_ = nullptr;
+            coef_cap_ = 0;
+            const size_t new_cap = std::max<size_t>(4096, need * 2);
+            HIP_CHECK(hipMalloc(&coef_, new_cap * sizeof(double)));
+            coef_cap_ = new_cap;
+        }
+        double* d_logw = coef_ + 3 * n_c;
+        int32_t* d_excl = reinterpret_cast<int32_t*>(d_logw + K);
+        const size_t up_doubles = (custom_w ? (size_t)K : 0) + n_excl;
+        if (up_doubles) {
+            double* h = reinterpret_cast<double*>(g_ws.stage(up_doubles * 8, st));
+            double* p = h;
+            if (custom_w) { memcpy(p, logw.data(), (size_t)K * 8); p += K; }
+            if (n_excl) {
+                p[n_excl - 1] = 0.0;  // defined padding for odd E
+                memcpy(p, excl.data(), (size_t)E * 4);
+            }
+            HIP_CHECK(hipMemcpyAsync(custom_w ? d_logw : d_logw + K, h,
+                                     up_doubles * 8, hipMemcpyHostToDevice, st));
+            if (guard_staging) g_ws.end_uploads_async(st);
+        }
+        const int64_t n_tiles = std::max<int64_t>(1, (Nv + FUSED_TILE - 1) / FUSED_TILE);
+        hipLaunchKernelGGL(k_fused_fit, dim3((unsigned)n_tiles, (unsigned)D_),
+                           dim3(FUSED_TILE), 0, st, params_, sorted_, sorted_cap_,
+                           Nv, d_excl, (int)E, domain_, Na, D_,
+                           consider_endpoints ? 1 : 0, magic_clip ? 1 : 0, coef_,
+                           coef_ + n_c, coef_ + 2 * n_c,
+                           custom_w ? nullptr : d_logw, w_num, w_start, w_step,
+                           log_total, prior_weight);
+        HIP_CHECK(hipGetLastError());
+        prep_.n = n_;
+        prep_.n_sorted = n_sorted_;
+        prep_.Na = Na;
+        prep_.w_num = w_num;
+        prep_.w_start = w_start;
+        prep_.w_step = w_step;
+        prep_.log_total = log_total;
+        prep_.prior_weight = prior_weight;
+        prep_.consider_endpoints = consider_endpoints;
+        prep_.magic_clip = magic_clip;
+        prep_.excl.assign(excl.data(), excl.data() + E);
+        prep_.logw.assign(logw.data(), logw.data() + logw.size());
+        prep_.valid = true;
+    }
+
     void ensure_sorted_capacity(int64_t need, hipStream_t st) {
         if (need <= sorted_cap_) return;
         const int64_t new_cap = std::max<int64_t>(1024, need * 2);
@@ -1937,6 +2177,12 @@ class TpeDeviceHistory {
     double* domain_ = nullptr;  // alow | ahigh | steps | n_choices
     bool has_steps_ = false;
     bool has_categorical_ = false;
+    // Above-set coefficients of the fused suggest: owned by the history (the
+    // shared workspace is laid over by every other entry point), grown
+    // geometrically.
+    double* coef_ = nullptr;
+    size_t coef_cap_ = 0;
+    PreparedFit prep_;
 };
 
 
@@ -2686,6 +2932,13 @@ PYBIND11_MODULE(_hipcore, m) {
         .def("sorted_index", &TpeDeviceHistory::sorted_index)
         .def("set_domain", &TpeDeviceHistory::set_domain, py::arg("alow"),
              py::arg("ahigh"), py::arg("steps"), py::arg("n_choices"))
+        .def("fused_prepare", &TpeDeviceHistory::fused_prepare, py::arg("excl"),
+             py::arg("n_above"), py::arg("logw") = arr_f64(),
+             py::arg("w_num") = 0, py::arg("w_start") = 1.0,
+             py::arg("w_step") = 0.0, py::arg("log_total") = 0.0,
+             py::arg("prior_weight") = 1.0,
+             py::arg("consider_endpoints") = false,
+             py::arg("magic_clip") = true)
         .def("fused_score", &TpeDeviceHistory::fused_score, py::arg("excl"),
              py::arg("n_above"), py::arg("x"), py::arg("xedges"),
              py::arg("bmu"), py::arg("bsig"), py::arg("bw"),

@@ -9,10 +9,16 @@ Three device modes:
   24 candidates — the fp64 observation matrix never crosses PCIe again. Subset
   compaction, the K1 fit and the K2 scoring all run on device.
 * **Fused suggest** (`fused_eligible`): for joint scoring over numerical dims the
-  whole suggest is one native call — a single packed upload (candidates, the
-  below estimator's kernels, the short list of excluded rows), a fit straight
-  from the resident sorted index, scoring, and the below log-pdf and EI
-  difference in the merge stage. No O(N) array is built or uploaded.
+  suggest is two native calls on one stream, and no O(N) array is built or
+  uploaded. `prepare_fused_resident` runs right after the below/above split:
+  it uploads the short list of excluded rows and launches the above-set fit
+  straight from the resident sorted index, into a coefficient buffer the
+  history owns, and returns without waiting — the fit runs while the host
+  builds the below estimator and draws the candidates. The scoring call then
+  makes one packed upload (candidates, the below estimator's kernels), scores
+  the above slices and the below mixture side by side in one launch, and a
+  small merge launch writes `log l - log g`. The native side checks that the
+  prepared fit still matches its arguments and otherwise fits by itself.
 * **Stateless scoring** (`kde_logpdf`): used by golden tests and the
   constant-liar path (whose observation set includes rows not in the table).
 
@@ -55,7 +61,7 @@ def device_ready(n_kernels: int) -> bool:
 
 
 # Limits of the fused entry point (LDS-cached exclusion list, below kernels
-# evaluated by one block per candidate); mirrored in tpe_core.hip.
+# fitted inside the scoring launch); mirrored in tpe_core.hip.
 FUSED_MAX_EXCL = 1024
 FUSED_MAX_BELOW = 1024
 
@@ -81,7 +87,7 @@ def fused_eligible(
 
     The fused kernels address the "above" set as the ascending-row complement
     of a short exclusion list, score jointly, and evaluate the below mixture
-    inside the merge stage; every other case keeps the unfused path.
+    inside the scoring launch; every other case keeps the unfused path.
     """
     return (
         fused_enabled()
@@ -225,6 +231,8 @@ class _SpaceDeviceMirror:
         # Device-resident sorted index bookkeeping: table rows the resident
         # index already covers (-1: never uploaded).
         self._rows_sorted_synced = -1
+        # (key, native fit arguments) of a prepare_fused not yet scored.
+        self._prepared: tuple | None = None
 
     def sync(self, cache: "_SpaceCache") -> None:
         n_total = len(cache.valid)
@@ -332,6 +340,58 @@ class _SpaceDeviceMirror:
         )
 
 
+    def prepare_fused(
+        self,
+        cache: "_SpaceCache",
+        below_rows: np.ndarray,
+        n_above: int,
+        weights: np.ndarray | None,
+        consider_endpoints: bool,
+        consider_magic_clip: bool,
+        prior_weight: float,
+    ) -> None:
+        """First half of a fused suggest: bring the mirror up to date, build
+        the exclusion list and launch the above-set fit, without waiting for
+        it. Everything it needs is known right after the below/above split, so
+        the fit runs on the GPU while the host builds the below estimator and
+        draws the candidates. ``weights`` as in ``score_fused``."""
+        self.sync(cache)
+        excl = cache.excluded_rows(below_rows)
+        if weights is None:
+            logw = _EMPTY_F64
+            ramp = default_weight_ramp(n_above, prior_weight)
+        else:
+            with np.errstate(divide="ignore"):
+                logw = np.log(weights)
+            ramp = (0, 1.0, 0.0, 0.0)
+        fit_args = (
+            excl,
+            int(n_above),
+            logw,
+            *ramp,
+            float(prior_weight),
+            consider_endpoints,
+            consider_magic_clip,
+        )
+        self._hist.fused_prepare(*fit_args)
+        # score_fused takes these arguments over as they are when it is asked
+        # for the same suggest (same split of the same table); the arrays are
+        # held so that their identities stay theirs.
+        key = self._suggest_key(
+            cache, below_rows, n_above, weights, consider_endpoints, consider_magic_clip,
+            prior_weight,
+        )
+        self._prepared = (key, fit_args, below_rows, weights)
+
+    @staticmethod
+    def _suggest_key(
+        cache, below_rows, n_above, weights, consider_endpoints, consider_magic_clip, prior_weight
+    ) -> tuple:
+        return (
+            len(cache.valid), id(below_rows), int(n_above), id(weights),
+            consider_endpoints, consider_magic_clip, float(prior_weight),
+        )
+
     def score_fused(
         self,
         cache: "_SpaceCache",
@@ -345,26 +405,26 @@ class _SpaceDeviceMirror:
         """Acquisition values through the fused entry point: one packed
         upload, no O(N) host arrays. ``weights`` is the normalized (n_above+1,)
         mixture weight vector of a custom weights function, or None for the
-        default ramp."""
-        self.sync(cache)
-        excl = cache.excluded_rows(req.below_rows)
+        default ramp. A ``prepare_fused`` for the same suggest has normally
+        run already; if not, it runs here (the native side then still finds
+        its fit prepared, just not early)."""
+        args = (
+            cache, req.below_rows, req.n_above, weights, consider_endpoints,
+            consider_magic_clip, prior_weight,
+        )
+        if self._prepared is None or self._prepared[0] != self._suggest_key(*args):
+            self.prepare_fused(*args)
+        assert self._prepared is not None
+        fit_args, self._prepared = self._prepared[1], None
+        excl, n_above, logw, w_num, w_start, w_step, log_total = fit_args[:7]
         x = req.x_raw
         xedges = _cell_edges(x, self._is_log, self._steps) if self._has_steps else _EMPTY_F64
         if self._is_log.any():
             x = x.copy()
             x[:, self._is_log] = np.log(x[:, self._is_log])
-        if weights is None:
-            logw = _EMPTY_F64
-            w_num, w_start, w_step, log_total = default_weight_ramp(
-                req.n_above, prior_weight
-            )
-        else:
-            with np.errstate(divide="ignore"):
-                logw = np.log(weights)
-            w_num, w_start, w_step, log_total = 0, 1.0, 0.0, 0.0
         return self._hist.fused_score(
             excl,
-            int(req.n_above),
+            n_above,
             x,
             xedges,
             req.below_mus,
@@ -380,6 +440,35 @@ class _SpaceDeviceMirror:
             consider_magic_clip,
             return_parts,
         )
+
+
+def _mirror_of(cache: "_SpaceCache") -> _SpaceDeviceMirror:
+    mirror = getattr(cache, "_device_mirror", None)
+    if mirror is None:
+        mirror = _SpaceDeviceMirror(cache.space)
+        cache._device_mirror = mirror  # type: ignore[attr-defined]
+    return mirror
+
+
+def prepare_fused_resident(
+    cache: "_SpaceCache",
+    below_rows: np.ndarray,
+    n_above: int,
+    weights: np.ndarray | None,
+    consider_endpoints: bool,
+    consider_magic_clip: bool,
+    prior_weight: float = 1.0,
+) -> None:
+    """Launch the above-set fit of a fused suggest ahead of its scoring call
+    (``score_above_resident(..., fused=...)`` with the same ``below_rows``
+    object, ``n_above`` and ``weights``). Purely an early start: scoring
+    without it, or after the table changed, fits by itself."""
+    if not _hip.is_available():
+        return
+    _mirror_of(cache).prepare_fused(
+        cache, below_rows, n_above, weights, consider_endpoints, consider_magic_clip,
+        prior_weight,
+    )
 
 
 def score_above_resident(
@@ -402,10 +491,7 @@ def score_above_resident(
     With ``fused`` (see ``fused_eligible``) the call returns the acquisition
     values ``log l(x) - log g(x)`` instead; ``sel`` and ``samples`` are unused
     and ``weights=None`` selects the default weight ramp, written on device."""
-    mirror = getattr(cache, "_device_mirror", None)
-    if mirror is None:
-        mirror = _SpaceDeviceMirror(cache.space)
-        cache._device_mirror = mirror  # type: ignore[attr-defined]
+    mirror = _mirror_of(cache)
     if fused is not None:
         return mirror.score_fused(
             cache, fused, weights, consider_endpoints, consider_magic_clip, prior_weight

@@ -516,6 +516,23 @@ class TPESampler(BaseSampler):
             and _device.device_ready(n_above + n_liar + 1)
         )
         fused = fused and use_device
+        fused_weights: np.ndarray | None = None
+        if fused:
+            # Everything the above-set fit needs is known here: launch it now
+            # so it runs on the GPU under the host work below (the below
+            # estimator and the candidate draw).
+            p = self._parzen_estimator_parameters
+            if p.weights is not default_weights:
+                fused_weights = self._above_weights(n_above)
+            _device.prepare_fused_resident(
+                cache,
+                below_rows,
+                n_above,
+                fused_weights,
+                p.consider_endpoints,
+                p.consider_magic_clip,
+                prior_weight=p.prior_weight,
+            )
 
         obs_above: dict[str, np.ndarray] = {}
         orders_above: dict[str, np.ndarray] | None = None
@@ -550,15 +567,16 @@ class TPESampler(BaseSampler):
         # host (it also drives candidate sampling). The host path remains for
         # small histories and custom estimator classes.
         if fused:
-            # One native call: fit, scoring, the below mixture and the EI
-            # difference all run on device; the below estimator above only
-            # drew the candidates (its scoring coefficients stay unbuilt).
+            # Scoring of the above mixture (fitted by the prepare call above),
+            # the below mixture and the EI difference all run on device; the
+            # below estimator only drew the candidates (its scoring
+            # coefficients stay unbuilt).
             assert x_below is not None
             p = self._parzen_estimator_parameters
             acq_func_vals = _device.score_above_resident(
                 cache,
                 None,
-                None if p.weights is default_weights else self._above_weights(n_above),
+                fused_weights,
                 None,
                 p.consider_endpoints,
                 p.consider_magic_clip,
