@@ -2657,6 +2657,220 @@ class Hssp3dSession {
 
 
 // ---------------------------------------------------------------------------
+// K6c/K6d: 4-objective hypervolume and greedy HSSP. The kernels and the
+// algorithm notes live in mo4d_kernels.h; these are the host entry points,
+// mirroring the 3-D ones above.
+// ---------------------------------------------------------------------------
+#include "mo4d_kernels.h"
+
+// 4-D hypervolume of points strictly inside ref, in any order. Host prep
+// builds the three stable sorted views (N log N, negligible next to the N^3
+// sweep); each block writes one partial and the host sums them in block order.
+double hv4d(const arr_f64& pts, double ref_w, double ref_x, double ref_y,
+            double ref_z) {
+    if (pts.ndim() != 2 || pts.shape(1) != 4)
+        throw std::runtime_error("hv4d: pts must be (N, 4)");
+    const int64_t N = pts.shape(0);
+    if (N == 0) return 0.0;
+    if (N > (int64_t)65535 * HV4_TILE)
+        throw std::runtime_error("hv4d: too many points");
+    const double* P = pts.data();
+    std::vector<int64_t> ow(N), ox(N), oy(N);
+    for (int64_t i = 0; i < N; ++i) ow[i] = ox[i] = oy[i] = i;
+    auto by_col = [&](int col) {
+        return [P, col](int64_t a, int64_t b) { return P[a * 4 + col] < P[b * 4 + col]; };
+    };
+    std::stable_sort(ow.begin(), ow.end(), by_col(0));
+    std::stable_sort(ox.begin(), ox.end(), by_col(1));
+    std::stable_sort(oy.begin(), oy.end(), by_col(2));
+    std::vector<double> ws(N), xs(N), yv(N), zv(N);
+    std::vector<int32_t> rank_w(N), rank_x(N), rw(N), rx(N);
+    for (int64_t i = 0; i < N; ++i) {
+        ws[i] = P[ow[i] * 4];
+        xs[i] = P[ox[i] * 4 + 1];
+        rank_w[ow[i]] = (int32_t)i;
+        rank_x[ox[i]] = (int32_t)i;
+    }
+    for (int64_t i = 0; i < N; ++i) {
+        yv[i] = P[oy[i] * 4 + 2];
+        zv[i] = P[oy[i] * 4 + 3];
+        rw[i] = rank_w[oy[i]];
+        rx[i] = rank_x[oy[i]];
+    }
+    const int64_t tiles = (N + HV4_TILE - 1) / HV4_TILE;
+    const int64_t n_part = tiles * tiles;
+    hipStream_t st = g_ws.get_stream();
+    double* base = g_ws.ensure(4 * (size_t)N + (size_t)n_part + (size_t)N + 8);
+    double* d_ws = base;
+    double* d_xs = d_ws + N;
+    double* d_yv = d_xs + N;
+    double* d_zv = d_yv + N;
+    double* d_out = d_zv + N;
+    int32_t* d_rw = reinterpret_cast<int32_t*>(d_out + n_part);
+    int32_t* d_rx = d_rw + N;
+    g_ws.begin_uploads();
+    g_ws.h2d(d_ws, ws.data(), N * 8, st);
+    g_ws.h2d(d_xs, xs.data(), N * 8, st);
+    g_ws.h2d(d_yv, yv.data(), N * 8, st);
+    g_ws.h2d(d_zv, zv.data(), N * 8, st);
+    g_ws.h2d(d_rw, rw.data(), N * 4, st);
+    g_ws.h2d(d_rx, rx.data(), N * 4, st);
+    hipLaunchKernelGGL(k_hv4d, dim3((unsigned)tiles, (unsigned)tiles),
+                       dim3(HV4_THREADS), 0, st, d_ws, d_xs, d_yv, d_zv, d_rw,
+                       d_rx, N, ref_w, ref_x, ref_y, ref_z, d_out);
+    std::vector<double> part(n_part);
+    HIP_CHECK(hipMemcpyAsync(part.data(), d_out, n_part * 8,
+                             hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    double hv = 0.0;
+    for (double v : part) hv += v;
+    return hv;
+}
+
+static size_t hssp4d_lds_bytes(int64_t kcap) { return (size_t)kcap * 24; }
+
+// Per-candidate greedy-HSSP contributions against a selected set passed as its
+// six pre-sorted views. Stateless; the session below is the production path.
+py::array_t<double> hssp4d_contrib(const arr_f64& cand, const arr_f64& sw,
+                                   const arr_f64& sx, const arr_f64& sy,
+                                   const arr_f64& syz, const arr_i32& syrw,
+                                   const arr_i32& syrx, double ref_w,
+                                   double ref_x, double ref_y, double ref_z) {
+    if (cand.ndim() != 2 || cand.shape(1) != 4)
+        throw std::runtime_error("hssp4d_contrib: cand must be (n, 4)");
+    const int64_t n = cand.shape(0);
+    const int64_t k = sw.size();
+    if ((int64_t)sx.size() != k || (int64_t)sy.size() != k ||
+        (int64_t)syz.size() != k || (int64_t)syrw.size() != k ||
+        (int64_t)syrx.size() != k)
+        throw std::runtime_error("hssp4d_contrib: ragged sorted views");
+    if (k > HSSP4_MAX_K)
+        throw std::runtime_error("hssp4d_contrib: selected set exceeds the LDS stream bound");
+    py::array_t<double> out(n);
+    if (n == 0) return out;
+    hipStream_t st = g_ws.get_stream();
+    double* base = g_ws.ensure((size_t)n * 4 + 4 * (size_t)k + n + (size_t)k + 8);
+    double* d_cand = base;
+    double* d_sw = d_cand + (size_t)n * 4;
+    double* d_sx = d_sw + k;
+    double* d_sy = d_sx + k;
+    double* d_syz = d_sy + k;
+    double* d_out = d_syz + k;
+    int32_t* d_syrw = reinterpret_cast<int32_t*>(d_out + n);
+    int32_t* d_syrx = d_syrw + k;
+    g_ws.begin_uploads();
+    g_ws.h2d(d_cand, cand.data(), (size_t)n * 4 * 8, st);
+    if (k > 0) {
+        g_ws.h2d(d_sw, sw.data(), k * 8, st);
+        g_ws.h2d(d_sx, sx.data(), k * 8, st);
+        g_ws.h2d(d_sy, sy.data(), k * 8, st);
+        g_ws.h2d(d_syz, syz.data(), k * 8, st);
+        g_ws.h2d(d_syrw, syrw.data(), k * 4, st);
+        g_ws.h2d(d_syrx, syrx.data(), k * 4, st);
+    }
+    hipLaunchKernelGGL(k_hssp4d_contrib, dim3((unsigned)n), dim3(HSSP4_THREADS),
+                       hssp4d_lds_bytes(k), st, d_cand, d_sw, d_sx, d_sy, d_syz,
+                       d_syrw, d_syrx, k, k, ref_w, ref_x, ref_y, ref_z, d_out);
+    HIP_CHECK(hipMemcpyAsync(out.mutable_data(), d_out, n * 8,
+                             hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    return out;
+}
+
+// Greedy-HSSP driver, 4 objectives: candidates, the taken-mask, the sorted
+// selected-set views and the per-round winner all stay on device.
+class Hssp4dSession {
+  public:
+    Hssp4dSession(const arr_f64& cand, double rw, double rx, double ry, double rz)
+        : rw_(rw), rx_(rx), ry_(ry), rz_(rz) {
+        if (cand.ndim() != 2 || cand.shape(1) != 4)
+            throw std::runtime_error("Hssp4dSession: cand must be (n, 4)");
+        n_ = cand.shape(0);
+        if (n_ == 0) return;
+        hipStream_t st = g_ws.get_stream();
+        HIP_CHECK(hipMalloc(&d_cand_, (size_t)n_ * 4 * 8));
+        HIP_CHECK(hipMalloc(&d_out_, (size_t)n_ * 8 + 8 + n_));
+        d_idx_ = reinterpret_cast<int64_t*>(d_out_ + n_);
+        d_taken_ = reinterpret_cast<uint8_t*>(d_idx_ + 1);
+        HIP_CHECK(hipMemcpyAsync(d_cand_, cand.data(), (size_t)n_ * 4 * 8,
+                                 hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemsetAsync(d_taken_, 0, n_, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    ~Hssp4dSession() {
+        if (d_cand_) (void)hipFree(d_cand_);
+        if (d_out_) (void)hipFree(d_out_);
+    }
+    Hssp4dSession(const Hssp4dSession&) = delete;
+    Hssp4dSession& operator=(const Hssp4dSession&) = delete;
+
+    // Launch-train greedy: the contrib -> argmax -> insert round is captured
+    // once as a linear three-kernel hipGraph (k and the round index live in
+    // device memory, so every round has identical arguments) and replayed
+    // subset_size times; ONE host sync at the end.
+    py::array_t<int64_t> run(int64_t subset_size) {
+        if (subset_size < 0)
+            throw std::runtime_error("Hssp4dSession.run: negative subset_size");
+        if (subset_size > n_) subset_size = n_;
+        if (subset_size > HSSP4_MAX_K)
+            throw std::runtime_error(
+                "Hssp4dSession.run: subset_size exceeds the insert staging bound");
+        py::array_t<int64_t> out(subset_size);
+        if (subset_size == 0) return out;
+        hipStream_t st = g_ws.get_stream();
+        const size_t kcap = (size_t)subset_size + 1;
+        double* base = g_ws.ensure(5 * kcap + subset_size + 6);
+        double* d_sw = base;
+        double* d_sx = d_sw + kcap;
+        double* d_sy = d_sx + kcap;
+        double* d_syz = d_sy + kcap;
+        int32_t* d_syrw = reinterpret_cast<int32_t*>(d_syz + kcap);
+        int32_t* d_syrx = d_syrw + kcap;  // the two rank arrays fill kcap doubles
+        int64_t* d_k = reinterpret_cast<int64_t*>(base + 5 * kcap);
+        int64_t* d_round = d_k + 1;
+        int64_t* d_chosen = d_round + 1;
+        HIP_CHECK(hipMemsetAsync(d_k, 0, 16, st));
+        HIP_CHECK(hipMemsetAsync(d_taken_, 0, n_, st));
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        hipLaunchKernelGGL(k_hssp4d_contrib_dk, dim3((unsigned)n_),
+                           dim3(HSSP4_THREADS), hssp4d_lds_bytes(kcap), st,
+                           d_cand_, d_sw, d_sx, d_sy, d_syz, d_syrw, d_syrx, d_k,
+                           (int64_t)kcap, rw_, rx_, ry_, rz_, d_out_);
+        hipLaunchKernelGGL(k_hssp3d_argmax, dim3(1), dim3(256), 0, st, d_out_,
+                           n_, d_taken_, d_idx_);
+        hipLaunchKernelGGL(k_hssp4d_insert, dim3(1), dim3(HSSP4_THREADS), 0, st,
+                           d_cand_, d_idx_, d_sw, d_sx, d_sy, d_syz, d_syrw,
+                           d_syrx, d_k, d_chosen, d_round);
+        HIP_CHECK(hipStreamEndCapture(st, &graph));
+        HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        hipError_t err = hipSuccess;
+        for (int64_t r = 0; r < subset_size && err == hipSuccess; ++r)
+            err = hipGraphLaunch(exec, st);
+        (void)hipGraphExecDestroy(exec);
+        (void)hipGraphDestroy(graph);
+        HIP_CHECK(err);
+        HIP_CHECK(hipMemcpyAsync(out.mutable_data(), d_chosen, subset_size * 8,
+                                 hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipGetLastError());
+        return out;
+    }
+
+  private:
+    int64_t n_ = 0;
+    double rw_, rx_, ry_, rz_;
+    double* d_cand_ = nullptr;
+    double* d_out_ = nullptr;
+    int64_t* d_idx_ = nullptr;
+    uint8_t* d_taken_ = nullptr;
+};
+
+
+// ---------------------------------------------------------------------------
 // K5: fused GP log-EI forward + gradient over a device-resident GP.
 //
 // The torch path spends ~50 launches per batched acquisition evaluation
@@ -2914,6 +3128,18 @@ PYBIND11_MODULE(_hipcore, m) {
     m.def("hssp3d_contrib", &hssp3d_contrib, py::arg("cand"), py::arg("sx"),
           py::arg("sxz"), py::arg("sy"), py::arg("syz"), py::arg("syr"),
           py::arg("ref_x"), py::arg("ref_y"), py::arg("ref_z"));
+    m.def("hv4d", &hv4d, py::arg("pts"), py::arg("ref_w"), py::arg("ref_x"),
+          py::arg("ref_y"), py::arg("ref_z"));
+    m.def("hssp4d_contrib", &hssp4d_contrib, py::arg("cand"), py::arg("sw"),
+          py::arg("sx"), py::arg("sy"), py::arg("syz"), py::arg("syrw"),
+          py::arg("syrx"), py::arg("ref_w"), py::arg("ref_x"), py::arg("ref_y"),
+          py::arg("ref_z"));
+    py::class_<Hssp4dSession>(m, "Hssp4dSession")
+        .def(py::init<const arr_f64&, double, double, double, double>(),
+             py::arg("cand"), py::arg("ref_w"), py::arg("ref_x"),
+             py::arg("ref_y"), py::arg("ref_z"))
+        .def("run", &Hssp4dSession::run, py::arg("subset_size"));
+    m.attr("HSSP4D_MAX_SUBSET") = py::int_(HSSP4_MAX_K);
     m.def("kde_logpdf", &kde_logpdf, py::arg("obs"), py::arg("sorted_pos"),
           py::arg("logw"), py::arg("alow"), py::arg("ahigh"), py::arg("steps"),
           py::arg("n_choices"), py::arg("prior_weight"),

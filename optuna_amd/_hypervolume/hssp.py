@@ -3,7 +3,9 @@
 3-objective fronts above a size threshold run the K6b HIP path: every greedy
 round evaluates ALL candidates' exclusive contributions in one kernel launch
 (one workgroup per candidate, selected set staged in LDS), replacing the
-host's lazy-heap sequence of WFG evaluations.
+host's lazy-heap sequence of WFG evaluations. 4-objective fronts take the same
+route through the K6d kernels (``k_hssp4d_*``): the selected set's sorted views
+stay on device and the contribution kernel stages the y-ordered stream in LDS.
 
 2-D uses an exact O(k·n) shrinking-corner greedy that is valid for arbitrary
 inputs (dominated and boundary points included); N-D uses greedy selection
@@ -81,6 +83,17 @@ def _solve_hssp_on_unique(
         and np.isfinite(loss_vals).all()
     ):
         device_choice = _solve_hssp_3d_device(
+            loss_vals, indices, subset_size, reference_point
+        )
+        if device_choice is not None:
+            return device_choice
+    if (
+        loss_vals.shape[1] == 4
+        and subset_size <= _DEVICE_HSSP4D_MAX_SUBSET
+        and len(loss_vals) * subset_size >= _DEVICE_HSSP4D_MIN_WORK
+        and np.isfinite(loss_vals).all()
+    ):
+        device_choice = _solve_hssp_4d_device(
             loss_vals, indices, subset_size, reference_point
         )
         if device_choice is not None:
@@ -181,6 +194,42 @@ def _solve_hssp_3d_device(
     # device; contrib -> masked argmax -> sorted insert repeat subset_size
     # times and a single sync brings back the chosen indices.
     session = core.Hssp3dSession(cand, rx, ry, rz)
+    chosen = np.asarray(session.run(int(subset_size)))
+    assert (chosen >= 0).all()
+    return indices[chosen]
+
+
+# 4-D gate on candidates x selections. The host lazy greedy pays one pure-Python
+# WFG per stale heap entry, so the device wins almost at once; its floor is the
+# ~0.4 ms graph instantiate plus launch train. The gate is the smallest size of
+# the HSSP sweep of scripts/hssp4d_timing.py (docs/PERF.md, "4-objective
+# hypervolume and HSSP") at which the device won by at least 2x: 10 candidates
+# x 3 selections (1.4 ms host, 0.39 ms device); 8 x 2 was 1.7x.
+_DEVICE_HSSP4D_MIN_WORK = 30
+# The insert kernel stages the shifting tails in registers (8 slots x 256
+# lanes) and the contribution kernel keeps the y-stream in LDS; both bound the
+# selected set at 2048. Larger subsets stay on the host path.
+_DEVICE_HSSP4D_MAX_SUBSET = 2048
+
+
+def _solve_hssp_4d_device(
+    vals: np.ndarray,
+    indices: np.ndarray,
+    subset_size: int,
+    reference_point: np.ndarray,
+) -> np.ndarray | None:
+    """Exact (non-lazy) greedy via the K6d launch train, or None without a device.
+
+    Same scheme as the 3-D session: contrib -> masked argmax -> sorted insert,
+    captured once as a hipGraph and replayed ``subset_size`` times with a
+    single sync at the end."""
+    from optuna_amd import _hip
+
+    core = _hip.get()
+    if core is None or not core.available():
+        return None
+    cand = np.ascontiguousarray(vals, dtype=np.float64)
+    session = core.Hssp4dSession(cand, *(float(v) for v in reference_point))
     chosen = np.asarray(session.run(int(subset_size)))
     assert (chosen >= 0).all()
     return indices[chosen]

@@ -4,9 +4,11 @@
 maintains the dominated 2-D staircase incrementally; N-D uses the WFG
 exclusive-volume recursion with limited-set Pareto filtering.
 
-On device, large-N dominance filtering and the 2-D/3-D paths are the K6 HIP
-kernels; the WFG recursion stays on host (irregular control flow) feeding the
-device with batched 2-D/3-D subproblems.
+On device, large-N dominance filtering and the 3-D and 4-D paths are the K6
+HIP kernels: 3-D is a per-prefix staircase sweep (``k_hv3d``), 4-D the same
+sweep nested once more over (w-rank, x-rank) pairs (``k_hv4d``). Both engage
+above a row gate and only when a GPU is present; five objectives and more stay
+on the host WFG recursion (irregular control flow).
 
 Parity: reference ``optuna/_hypervolume/wfg.py`` (_compute_2d :8, _compute_3d :16,
 _compute_hv/_compute_exclusive_hv :41-107, compute_hypervolume :110).
@@ -140,6 +142,10 @@ def compute_hypervolume(
             if dev is not None:
                 return dev
         return _compute_3d(sorted_pareto_sols, reference_point)
+    if reference_point.shape[0] == 4 and len(sorted_pareto_sols) >= _DEVICE_HV4D_MIN_ROWS:
+        dev = _hv4d_device(sorted_pareto_sols, reference_point)
+        if dev is not None:
+            return dev
     return _compute_hv(sorted_pareto_sols, reference_point)
 
 
@@ -161,5 +167,29 @@ def _hv3d_device(sorted_pts: np.ndarray, reference_point: np.ndarray) -> float |
             float(reference_point[0]),
             float(reference_point[1]),
             float(reference_point[2]),
+        )
+    )
+
+
+# 4-D: the host WFG recursion is pure Python and grows much faster than the
+# device's N^3 sweep, whose cost below ~100 rows is the ~0.1 ms launch and
+# copy-back. The gate is the smallest size of the hypervolume sweep of
+# scripts/hssp4d_timing.py (docs/PERF.md, "4-objective hypervolume and HSSP")
+# at which the device won by at least 2x: n = 6 (0.32 ms host, 0.11 ms
+# device); n = 4 was 1.3x.
+_DEVICE_HV4D_MIN_ROWS = 6
+
+
+def _hv4d_device(sorted_pts: np.ndarray, reference_point: np.ndarray) -> float | None:
+    """K6c HIP path: nested (w, x) prefix-pair staircase sweep (or None)."""
+    from optuna_amd import _hip
+
+    core = _hip.get()
+    if core is None or not core.available():
+        return None
+    return float(
+        core.hv4d(
+            np.ascontiguousarray(sorted_pts, dtype=np.float64),
+            *(float(v) for v in reference_point),
         )
     )
