@@ -15,7 +15,7 @@ from pathlib import Path
 
 HIP_ARCH = os.environ.get("OPTUNA_AMD_HIP_ARCH", "gfx950")
 _HIP_DIR = Path(__file__).resolve().parent
-_SRC = _HIP_DIR / "csrc" / "tpe_core.hip"
+_SRC = _HIP_DIR / "csrc" / "hipcore.hip"
 
 
 def _ext_suffix() -> str:

@@ -61,7 +61,7 @@ def device_ready(n_kernels: int) -> bool:
 
 
 # Limits of the fused entry point (LDS-cached exclusion list, below kernels
-# fitted inside the scoring launch); mirrored in tpe_core.hip.
+# fitted inside the scoring launch); mirrored in tpe_fused_kernels.h.
 FUSED_MAX_EXCL = 1024
 FUSED_MAX_BELOW = 1024
 

@@ -38,7 +38,7 @@ pytestmark = pytest.mark.gpu
 
 RTOL = 1e-9
 ATOL = 1e-9
-C = 64  # SCORE_SLICE of tpe_core.hip
+C = 64  # SCORE_SLICE of tpe_fused_kernels.h
 
 
 @pytest.fixture(scope="module")
