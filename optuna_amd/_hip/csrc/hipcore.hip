@@ -53,6 +53,9 @@ PYBIND11_MODULE(_hipcore, m) {
           py::arg("n_choices"), py::arg("prior_weight"),
           py::arg("x"), py::arg("xedges"),
           py::arg("consider_endpoints") = false, py::arg("magic_clip") = true);
+    m.def("tpe_below_kernels", &tpe_below_kernels, py::arg("obs"),
+          py::arg("alow"), py::arg("ahigh"), py::arg("consider_endpoints"),
+          py::arg("consider_magic_clip"), py::arg("active"));
     py::class_<TpeDeviceHistory>(m, "TpeDeviceHistory")
         .def(py::init<int64_t>(), py::arg("dims"))
         .def_property_readonly("n_rows", &TpeDeviceHistory::n_rows)

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "hip_common.h"
+#include "tpe_below_host.h"
 #include "tpe_fused_kernels.h"
 #include "tpe_kernels.h"
 
@@ -112,6 +113,51 @@ py::array_t<double> kde_logpdf(const arr_f64& obs, const arr_i64& sorted_pos,
     HIP_CHECK(hipStreamSynchronize(st));
     HIP_CHECK(hipGetLastError());
     return out;
+}
+
+// Below estimator of a fused suggest, fitted on the host in one call (see
+// tpe_below_host.h): no device work. The arrays are taken as they are, so a
+// wrong dtype or a non-contiguous view is an error, not a silent copy.
+//   obs (n, D) f64, alow/ahigh (D,) f64, active (S,) i64 in [0, n]
+// returns (mus, sigmas (n + 1, D); a, b, loc, scale (S, D)).
+static const double* below_f64(const py::array& arr, const char* name) {
+    if (!py::isinstance<py::array_t<double>>(arr) ||
+        !(arr.flags() & py::array::c_style))
+        throw std::runtime_error(std::string("tpe_below_kernels: ") + name +
+                                 " must be a C-contiguous float64 array");
+    return static_cast<const double*>(arr.data());
+}
+
+py::tuple tpe_below_kernels(const py::array& obs, const py::array& alow,
+                            const py::array& ahigh, bool consider_endpoints,
+                            bool consider_magic_clip, const py::array& active) {
+    const double* p_obs = below_f64(obs, "obs");
+    const double* p_alow = below_f64(alow, "alow");
+    const double* p_ahigh = below_f64(ahigh, "ahigh");
+    if (!py::isinstance<py::array_t<int64_t>>(active) ||
+        !(active.flags() & py::array::c_style))
+        throw std::runtime_error(
+            "tpe_below_kernels: active must be a C-contiguous int64 array");
+    if (obs.ndim() != 2 || alow.ndim() != 1 || ahigh.ndim() != 1 ||
+        active.ndim() != 1 || obs.shape(1) < 1 || alow.shape(0) != obs.shape(1) ||
+        ahigh.shape(0) != obs.shape(1))
+        throw std::runtime_error("tpe_below_kernels: shape mismatch");
+    const int64_t n = obs.shape(0), D = obs.shape(1), S = active.shape(0);
+    if (n + 1 > FUSED_MAX_BELOW)
+        throw std::runtime_error("tpe_below_kernels: too many below kernels");
+    const int64_t* p_active = static_cast<const int64_t*>(active.data());
+    for (int64_t s = 0; s < S; ++s)
+        if (p_active[s] < 0 || p_active[s] > n)
+            throw std::runtime_error("tpe_below_kernels: active out of range");
+
+    py::array_t<double> mus({n + 1, D}), sigmas({n + 1, D});
+    py::array_t<double> a({S, D}), b({S, D}), loc({S, D}), scale({S, D});
+    tpe_below::fit_and_gather(p_obs, (size_t)n, (size_t)D, p_alow, p_ahigh,
+                              consider_endpoints, consider_magic_clip, p_active,
+                              (size_t)S, mus.mutable_data(), sigmas.mutable_data(),
+                              a.mutable_data(), b.mutable_data(),
+                              loc.mutable_data(), scale.mutable_data());
+    return py::make_tuple(mus, sigmas, a, b, loc, scale);
 }
 
 // ---------------------------------------------------------------------------

@@ -19,6 +19,11 @@ Three device modes:
   the above slices and the below mixture side by side in one launch, and a
   small merge launch writes `log l - log g`. The native side checks that the
   prepared fit still matches its arguments and otherwise fits by itself.
+  Between the two calls the below estimator is fitted by a third, host-only
+  native call (`draw_below_native` -> `tpe_below_kernels`) that repeats the
+  numpy arithmetic of `parzen.py` bit for bit; the truncated-normal quantile
+  and the RNG calls stay in Python. Custom weights functions and
+  `OPTUNA_AMD_TPE_NATIVE_BELOW=0` keep the Python estimator.
 * **Stateless scoring** (`kde_logpdf`): used by golden tests and the
   constant-liar path (whose observation set includes rows not in the table).
 
@@ -41,6 +46,8 @@ from optuna_amd.distributions import (
     FloatDistribution,
     IntDistribution,
 )
+from optuna_amd.samplers._tpe import _truncnorm_np as _tn
+from optuna_amd.samplers._tpe.parzen import _NumericalSpace, _to_param_domain
 
 
 if TYPE_CHECKING:
@@ -132,6 +139,61 @@ def expand_weight_ramp(n: int, prior_weight: float) -> np.ndarray:
         w[num - 1] = 1.0
     w[n] = prior_weight if n else 1.0
     return w
+
+
+def native_below_enabled() -> bool:
+    """``OPTUNA_AMD_TPE_NATIVE_BELOW=0`` keeps the below estimator of a fused
+    suggest in Python (A/B runs)."""
+    return os.environ.get("OPTUNA_AMD_TPE_NATIVE_BELOW", "1") != "0"
+
+
+_UNRESOLVED = object()
+
+
+def native_below(cache: "_SpaceCache"):
+    """The extension's ``tpe_below_kernels`` when the native below route is on
+    for this space, else None (switched off, or no extension loaded). Resolved
+    once per space cache."""
+    if not native_below_enabled():
+        return None
+    fn = getattr(cache, "_native_below", _UNRESOLVED)
+    if fn is _UNRESOLVED:
+        fn = getattr(_hip.get(), "tpe_below_kernels", None)
+        cache._native_below = fn  # type: ignore[attr-defined]
+    return fn
+
+
+def draw_below_native(
+    fn,
+    cache: "_SpaceCache",
+    below_rows: np.ndarray,
+    weights: np.ndarray,
+    rng: np.random.RandomState,
+    size: int,
+    consider_endpoints: bool,
+    consider_magic_clip: bool,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Candidates of a fused suggest with the below estimator fitted by ``fn``
+    (``tpe_below_kernels``): returns ``(x_raw (S, D), mus, sigmas (Kb, D))``.
+
+    Equal bit for bit to ``_ParzenEstimator(below observations)`` followed by
+    its ``_sample_array``: the same RNG calls in the same order, the same
+    truncated-normal quantile, and a fit that repeats numpy's arithmetic.
+    ``weights`` are that estimator's normalized mixture weights."""
+    ns = getattr(cache, "_numerical_space", None)
+    if ns is None:
+        ns = cache._numerical_space = _NumericalSpace.of(cache.dists)  # type: ignore[attr-defined]
+    obs = cache.params[below_rows[cache.valid[below_rows]]]  # a fresh (n, D) copy
+    if ns.is_log.any():
+        obs[:, ns.is_log] = np.log(obs[:, ns.is_log])
+    active = rng.choice(len(weights), p=weights, size=size)
+    mus, sigmas, a, b, loc, scale = fn(
+        obs, ns.adapted_lows, ns.adapted_highs, consider_endpoints, consider_magic_clip, active
+    )
+    q = rng.uniform(low=0, high=1, size=a.shape)
+    x = _tn.ppf(q, a, b) * scale + loc
+    _to_param_domain(x, ns.kinds, ns.lows, ns.highs, ns.steps)
+    return x, mus, sigmas
 
 
 class FusedRequest(NamedTuple):

@@ -75,6 +75,73 @@ class _CategoricalDim(NamedTuple):
     weights: np.ndarray  # (K, C)
 
 
+class _NumericalSpace(NamedTuple):
+    """Per-space constants of an all-numerical search space (no kernels)."""
+
+    kinds: np.ndarray  # (D,) int8 — KIND_* codes
+    lows: np.ndarray  # (D,) original domain low
+    highs: np.ndarray  # (D,) original domain high
+    steps: np.ndarray  # (D,) step or 0
+    adapted_lows: np.ndarray  # (D,) KDE-domain low  (step-widened, logged)
+    adapted_highs: np.ndarray  # (D,) KDE-domain high
+    is_log: np.ndarray  # (D,) bool
+
+    @classmethod
+    def of(cls, dists: list[BaseDistribution]) -> "_NumericalSpace":
+        steps = np.array(
+            [float(d.step) if d.step is not None else 0.0 for d in dists]
+        )
+        is_log = np.array([bool(d.log) for d in dists])
+        lows = np.array([float(d.low) for d in dists])
+        highs = np.array([float(d.high) for d in dists])
+        a_lows = np.where(steps != 0.0, lows - steps / 2, lows)
+        a_highs = np.where(steps != 0.0, highs + steps / 2, highs)
+        if is_log.any():
+            a_lows[is_log] = np.log(a_lows[is_log])
+            a_highs[is_log] = np.log(a_highs[is_log])
+        kinds = np.where(
+            is_log,
+            np.where(steps != 0.0, KIND_LOG_DISC, KIND_LOG),
+            np.where(steps != 0.0, KIND_DISC, KIND_CONT),
+        ).astype(np.int8)
+        return cls(kinds, lows, highs, steps, a_lows, a_highs, is_log)
+
+
+def _to_param_domain(
+    vals: np.ndarray, kinds: np.ndarray, lows: np.ndarray, highs: np.ndarray, steps: np.ndarray
+) -> None:
+    """KDE-domain draws (S, Dn) to parameter values, in place: log dims are
+    exponentiated, stepped dims rounded to their grid and clipped."""
+    is_log = (kinds == KIND_LOG) | (kinds == KIND_LOG_DISC)
+    vals[:, is_log] = np.exp(vals[:, is_log])
+    has_step = steps > 0
+    if np.any(has_step):
+        lo = lows[has_step]
+        st = steps[has_step]
+        hi = highs[has_step]
+        vals[:, has_step] = np.clip(
+            lo + np.round((vals[:, has_step] - lo) / st) * st, lo, hi
+        )
+
+
+def _mixture_weights(
+    parameters: _ParzenEstimatorParameters,
+    n_obs: int,
+    predetermined_weights: np.ndarray | None = None,
+) -> np.ndarray:
+    """Normalized (n_obs + 1,) kernel weights of an estimator, prior last."""
+    weights = (
+        predetermined_weights
+        if predetermined_weights is not None
+        else _ParzenEstimator._call_weights_func(parameters.weights, n_obs)
+    )
+    if n_obs == 0:
+        weights = np.array([1.0])
+    else:
+        weights = np.append(weights, [parameters.prior_weight])
+    return weights / weights.sum()
+
+
 class _ParzenEstimator:
     """Mixture of K product kernels over the search space (see module docstring)."""
 
@@ -103,17 +170,7 @@ class _ParzenEstimator:
 
         if predetermined_weights is not None:
             assert n_obs == len(predetermined_weights)
-        weights = (
-            predetermined_weights
-            if predetermined_weights is not None
-            else self._call_weights_func(parameters.weights, n_obs)
-        )
-        if n_obs == 0:
-            weights = np.array([1.0])
-        else:
-            weights = np.append(weights, [parameters.prior_weight])
-        weights = weights / weights.sum()
-        self._weights = weights
+        self._weights = _mixture_weights(parameters, n_obs, predetermined_weights)
         self._n_kernels = n_obs + 1
 
         # ---- build per-dimension model, packing numerical dims into SoA ------------
@@ -302,22 +359,7 @@ class _ParzenEstimator:
     ) -> _NumericalDims:
         """Vectorized equivalent of the per-dim `_numerical_kernels` loop."""
         D = len(dists)
-        steps = np.array(
-            [float(d.step) if d.step is not None else 0.0 for d in dists]
-        )
-        is_log = np.array([bool(d.log) for d in dists])
-        lows = np.array([float(d.low) for d in dists])
-        highs = np.array([float(d.high) for d in dists])
-        a_lows = np.where(steps != 0.0, lows - steps / 2, lows)
-        a_highs = np.where(steps != 0.0, highs + steps / 2, highs)
-        if is_log.any():
-            a_lows[is_log] = np.log(a_lows[is_log])
-            a_highs[is_log] = np.log(a_highs[is_log])
-        kinds = np.where(
-            is_log,
-            np.where(steps != 0.0, KIND_LOG_DISC, KIND_LOG),
-            np.where(steps != 0.0, KIND_DISC, KIND_CONT),
-        ).astype(np.int8)
+        kinds, lows, highs, steps, a_lows, a_highs, is_log = _NumericalSpace.of(dists)
 
         ranges = a_highs - a_lows
         if n_obs == 0:
@@ -498,16 +540,7 @@ class _ParzenEstimator:
             a = (num.adapted_lows[np.newaxis, :] - mus) / sigmas
             b = (num.adapted_highs[np.newaxis, :] - mus) / sigmas
             vals = _tn.rvs(a, b, loc=mus, scale=sigmas, random_state=rng)
-            is_log = (num.kinds == KIND_LOG) | (num.kinds == KIND_LOG_DISC)
-            vals[:, is_log] = np.exp(vals[:, is_log])
-            has_step = num.steps > 0
-            if np.any(has_step):
-                lo = num.lows[has_step]
-                st = num.steps[has_step]
-                hi = num.highs[has_step]
-                vals[:, has_step] = np.clip(
-                    lo + np.round((vals[:, has_step] - lo) / st) * st, lo, hi
-                )
+            _to_param_domain(vals, num.kinds, num.lows, num.highs, num.steps)
             out[:, num.dim_indices] = vals
         for cat in self._categoricals:
             active_w = cat.weights[active[:, cat.dim_index], :]
@@ -596,16 +629,7 @@ class _ParzenEstimator:
             a = (num.adapted_lows[np.newaxis, :] - mus) / sigmas
             b = (num.adapted_highs[np.newaxis, :] - mus) / sigmas
             vals = _tn.rvs(a, b, loc=mus, scale=sigmas, random_state=rng)
-            is_log = (num.kinds == KIND_LOG) | (num.kinds == KIND_LOG_DISC)
-            vals[:, is_log] = np.exp(vals[:, is_log])
-            has_step = num.steps > 0
-            if np.any(has_step):
-                lo = num.lows[has_step]
-                st = num.steps[has_step]
-                hi = num.highs[has_step]
-                vals[:, has_step] = np.clip(
-                    lo + np.round((vals[:, has_step] - lo) / st) * st, lo, hi
-                )
+            _to_param_domain(vals, num.kinds, num.lows, num.highs, num.steps)
             out[:, num.dim_indices] = vals
 
         for cat in self._categoricals:

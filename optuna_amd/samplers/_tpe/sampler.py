@@ -29,7 +29,11 @@ from optuna_amd.samplers._base import (
 )
 from optuna_amd.samplers._lazy_random_state import LazyRandomState
 from optuna_amd.samplers._random import RandomSampler
-from optuna_amd.samplers._tpe.parzen import _ParzenEstimator, _ParzenEstimatorParameters
+from optuna_amd.samplers._tpe.parzen import (
+    _mixture_weights,
+    _ParzenEstimator,
+    _ParzenEstimatorParameters,
+)
 from optuna_amd.search_space import IntersectionSearchSpace
 from optuna_amd.search_space.group_decomposed import (
     _GroupDecomposedSearchSpace,
@@ -459,7 +463,6 @@ class TPESampler(BaseSampler):
                 above_rows
             ):
                 return None
-        obs_below, orders_below = history.observations(search_space, below_rows, cache)
 
         # Constant-liar rows: other workers' RUNNING trials join the "above"
         # set (params shared via system attrs). As an (L, D) matrix they ride
@@ -517,11 +520,16 @@ class TPESampler(BaseSampler):
         )
         fused = fused and use_device
         fused_weights: np.ndarray | None = None
+        # Native below route: the below estimator of a fused suggest is fitted
+        # by one call into the extension instead of through numpy.
+        below_native = None
+        p = self._parzen_estimator_parameters
+        if fused and p.weights is default_weights and p.prior_weight >= 0:
+            below_native = _device.native_below(cache)
         if fused:
             # Everything the above-set fit needs is known here: launch it now
             # so it runs on the GPU under the host work below (the below
             # estimator and the candidate draw).
-            p = self._parzen_estimator_parameters
             if p.weights is not default_weights:
                 fused_weights = self._above_weights(n_above)
             _device.prepare_fused_resident(
@@ -546,20 +554,39 @@ class TPESampler(BaseSampler):
                 }
                 orders_above = None  # appended rows invalidate presorted orders
 
-        mpe_below = self._build_mpe(
-            study, search_space, obs_below, handle_below=True, orders=orders_below
-        )
-        x_below: np.ndarray | None = None
-        if per_dim:
-            samples_below = mpe_below.sample_per_dim(self._rng.rng, self._n_ei_candidates)
-        elif fused:
-            # Same draws as sample(); the fused entry takes the matrix as is.
-            x_below = mpe_below._sample_array(self._rng.rng, self._n_ei_candidates)
-            samples_below = {
-                name: x_below[:, i] for i, name in enumerate(mpe_below._param_names)
-            }
+        if below_native is not None:
+            # Same draws, kernels and weights as the estimator below would
+            # give; its scoring runs on device like that of any fused suggest.
+            below_weights = self._below_weights(n_below_valid, study._is_multi_objective())
+            x_below, below_mus, below_sigmas = _device.draw_below_native(
+                below_native,
+                cache,
+                below_rows,
+                below_weights,
+                self._rng.rng,
+                self._n_ei_candidates,
+                p.consider_endpoints,
+                p.consider_magic_clip,
+            )
+            samples_below = {name: x_below[:, i] for i, name in enumerate(cache.names)}
         else:
-            samples_below = mpe_below.sample(self._rng.rng, self._n_ei_candidates)
+            obs_below, orders_below = history.observations(search_space, below_rows, cache)
+            mpe_below = self._build_mpe(
+                study, search_space, obs_below, handle_below=True, orders=orders_below
+            )
+            if per_dim:
+                samples_below = mpe_below.sample_per_dim(self._rng.rng, self._n_ei_candidates)
+            elif fused:
+                # Same draws as sample(); the fused entry takes the matrix as is.
+                x_below = mpe_below._sample_array(self._rng.rng, self._n_ei_candidates)
+                samples_below = {
+                    name: x_below[:, i] for i, name in enumerate(mpe_below._param_names)
+                }
+                below_mus = mpe_below._numerical.mus
+                below_sigmas = mpe_below._numerical.sigmas
+                below_weights = mpe_below.weights
+            else:
+                samples_below = mpe_below.sample(self._rng.rng, self._n_ei_candidates)
 
         # Device path (K1+K2): the big "above" KDE is fit and scored against the
         # HBM-resident parameter table for every distribution type (continuous,
@@ -571,8 +598,6 @@ class TPESampler(BaseSampler):
             # the below mixture and the EI difference all run on device; the
             # below estimator only drew the candidates (its scoring
             # coefficients stay unbuilt).
-            assert x_below is not None
-            p = self._parzen_estimator_parameters
             acq_func_vals = _device.score_above_resident(
                 cache,
                 None,
@@ -585,9 +610,9 @@ class TPESampler(BaseSampler):
                     below_rows=below_rows,
                     n_above=n_above,
                     x_raw=x_below,
-                    below_mus=mpe_below._numerical.mus,
-                    below_sigmas=mpe_below._numerical.sigmas,
-                    below_weights=mpe_below.weights,
+                    below_mus=below_mus,
+                    below_sigmas=below_sigmas,
+                    below_weights=below_weights,
                 ),
             )
         elif use_device:
@@ -646,7 +671,15 @@ class TPESampler(BaseSampler):
                     samples_below[param_name][best].item()
                 )
             return ret
-        ret = TPESampler._compare(samples_below, acq_func_vals)
+        return self._best_candidate(search_space, samples_below, acq_func_vals)
+
+    @staticmethod
+    def _best_candidate(
+        search_space: dict[str, BaseDistribution],
+        samples: dict[str, np.ndarray],
+        acq_func_vals: np.ndarray,
+    ) -> dict[str, Any]:
+        ret = TPESampler._compare(samples, acq_func_vals)
 
         for param_name, dist in search_space.items():
             ret[param_name] = dist.to_external_repr(ret[param_name])
@@ -661,6 +694,20 @@ class TPESampler(BaseSampler):
         else:
             w = np.append(w, [p.prior_weight])
         return w / w.sum()
+
+    def _below_weights(self, n: int, multi_objective: bool) -> np.ndarray:
+        """Mixture weights the below estimator of n observations would carry
+        under ``default_weights`` (all-ones before the prior for a
+        multi-objective study), read-only. The last result is kept: n is
+        gamma(history size), which rarely changes from one suggest to the next."""
+        p = self._parzen_estimator_parameters
+        key = (n, multi_objective, p.prior_weight)
+        memo = getattr(self, "_below_weights_memo", None)
+        if memo is None or memo[0] != key:
+            w = _mixture_weights(p, n, np.ones(n) if multi_objective else None)
+            w.setflags(write=False)
+            memo = self._below_weights_memo = (key, w)
+        return memo[1]
 
     def _build_mpe(
         self,

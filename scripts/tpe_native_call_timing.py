@@ -3,7 +3,9 @@
 Runs the configuration of ``bench.py`` defaults (TPE, single objective, 10k
 history, 20 float dims, 24 candidates) and takes ``time.perf_counter`` around
 every ``TpeDeviceHistory.fused_score`` call and, separately, around every
-``fused_prepare`` call (a build without the early fit has none). Prints one
+``fused_prepare`` call (a build without the early fit has none), every
+``tpe_below_kernels`` call (the native fit of the below estimator; a build
+without it has none) and the whole of ``TPESampler._sample_locked``. Prints one
 JSON line with the median, the 10th/90th percentiles and min/max in
 microseconds, plus the suggest+tell rate of the timed steps.
 
@@ -76,7 +78,19 @@ def main() -> None:
     from optuna_amd.samplers._tpe import _device
 
     optuna_amd.logging.set_verbosity(optuna_amd.logging.WARNING)
-    times: dict[str, list[float]] = {"fused_score": [], "fused_prepare": []}
+    times: dict[str, list[float]] = {
+        "fused_score": [], "fused_prepare": [], "tpe_below_kernels": [], "sample_locked": [],
+    }
+
+    def timed(fn, bucket: list[float]):
+        def wrapper(*args, **kwargs):
+            t0 = time.perf_counter()
+            out = fn(*args, **kwargs)
+            bucket.append(time.perf_counter() - t0)
+            return out
+
+        return wrapper
+
     orig_init = _device._SpaceDeviceMirror.__init__
 
     def init(self, space):
@@ -84,6 +98,22 @@ def main() -> None:
         self._hist = _TimedHistory(self._hist, times)
 
     _device._SpaceDeviceMirror.__init__ = init
+    sampler_cls = optuna_amd.samplers.TPESampler
+    sampler_cls._sample_locked = timed(sampler_cls._sample_locked, times["sample_locked"])
+    # A build from before the native below route has no such entry.
+    orig_native = getattr(_device, "native_below", None)
+    if orig_native is not None:
+        wrapped: dict = {}
+
+        def native_below(cache):
+            fn = orig_native(cache)
+            if fn is None:
+                return None
+            if fn not in wrapped:
+                wrapped[fn] = timed(fn, times["tpe_below_kernels"])
+            return wrapped[fn]
+
+        _device.native_below = native_below
 
     names = [f"x{i}" for i in range(args.dims)]
     dists = {n: optuna_amd.distributions.FloatDistribution(-5.0, 5.0) for n in names}
@@ -130,6 +160,8 @@ def main() -> None:
                 "steps_per_s": round(args.steps / wall, 1),
                 "fused_score": _stats(times["fused_score"]),
                 "fused_prepare": _stats(times["fused_prepare"]),
+                "tpe_below_kernels": _stats(times["tpe_below_kernels"]),
+                "sample_locked": _stats(times["sample_locked"]),
             }
         ),
         flush=True,
