@@ -56,6 +56,7 @@ PYBIND11_MODULE(_hipcore, m) {
     m.def("tpe_below_kernels", &tpe_below_kernels, py::arg("obs"),
           py::arg("alow"), py::arg("ahigh"), py::arg("consider_endpoints"),
           py::arg("consider_magic_clip"), py::arg("active"));
+    tpe_draw_py::register_functions(m, (size_t)FUSED_MAX_BELOW);
     py::class_<TpeDeviceHistory>(m, "TpeDeviceHistory")
         .def(py::init<int64_t>(), py::arg("dims"))
         .def_property_readonly("n_rows", &TpeDeviceHistory::n_rows)
@@ -84,6 +85,17 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("log_total") = 0.0, py::arg("prior_weight") = 1.0,
              py::arg("consider_endpoints") = false,
              py::arg("magic_clip") = true, py::arg("return_parts") = false)
+        .def("fused_draw_score", &TpeDeviceHistory::fused_draw_score,
+             py::arg("excl"), py::arg("n_above"), py::arg("table"),
+             py::arg("valid"), py::arg("below_rows"), py::arg("bw"),
+             py::arg("u"), py::arg("q"), py::arg("alow"), py::arg("ahigh"),
+             py::arg("kinds"), py::arg("lows"), py::arg("highs"),
+             py::arg("steps"), py::arg("logw") = arr_f64(),
+             py::arg("w_num") = 0, py::arg("w_start") = 1.0,
+             py::arg("w_step") = 0.0, py::arg("log_total") = 0.0,
+             py::arg("prior_weight") = 1.0,
+             py::arg("consider_endpoints") = false,
+             py::arg("magic_clip") = true)
         .def("score", &TpeDeviceHistory::score, py::arg("sorted_rows"),
              py::arg("pos"), py::arg("n_above"), py::arg("logw"), py::arg("alow"),
              py::arg("ahigh"), py::arg("steps"), py::arg("n_choices"),

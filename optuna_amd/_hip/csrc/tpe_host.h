@@ -4,6 +4,7 @@
 
 #include "hip_common.h"
 #include "tpe_below_host.h"
+#include "tpe_draw_bind.h"
 #include "tpe_fused_kernels.h"
 #include "tpe_kernels.h"
 
@@ -476,6 +477,9 @@ class TpeDeviceHistory {
     //                  into pinned host memory: no download). It reuses
     //                  the prepared fit when that is still valid for its
     //                  arguments and otherwise runs the fit itself first.
+    //   fused_draw_score  the same device half behind the host draw of the
+    //                  candidates, with the arg-max behind it: the one call
+    //                  of the sampler's native draw route.
     //   excl     sorted table rows NOT in the above set (below + invalid rows)
     //   n_above  size of the above set (= resident index rows not in excl)
     //   x/xedges candidates (KDE domain); xedges only read for stepped dims
@@ -517,6 +521,107 @@ class TpeDeviceHistory {
             (has_steps_ && (int64_t)xedges.size() != 2 * S * D_))
             throw std::runtime_error("fused_score: shape mismatch");
 
+        // The results are allocated ahead of the call, under the device work.
+        py::array_t<double> lw(return_parts ? K : 0);
+        py::array_t<double> out(return_parts ? 0 : S);
+        const double* h_out = score_candidates(
+            excl, n_above, x.data(), xedges.data(), bmu.data(), bsig.data(),
+            bw.data(), S, Kb, logw, w_num, w_start, w_step, log_total,
+            prior_weight, consider_endpoints, magic_clip,
+            return_parts ? lw.mutable_data() : nullptr);
+        if (return_parts) {
+            py::array_t<double> parts({(int64_t)3, S});
+            memcpy(parts.mutable_data(), h_out, 3 * (size_t)S * 8);
+            return py::make_tuple(parts, lw);
+        }
+        memcpy(out.mutable_data(), h_out, (size_t)S * 8);
+        return out;
+    }
+
+    // Second half of a fused suggest in one call: the host draw of
+    // tpe_draw_bind.h (below fit, kernel choice, quantile, candidates and
+    // their scoring inputs), then the device half of fused_score, then the
+    // arg-max. Fit arguments as for fused_score; the estimator flags serve
+    // the below fit too. Returns (best index, x_raw (S, D), (S,) log l - log g).
+    py::tuple fused_draw_score(const arr_i32& excl, int64_t n_above,
+                               const py::array& table, const py::array& valid,
+                               const py::array& below_rows, const py::array& bw,
+                               const py::array& u, const py::array& q,
+                               const py::array& alow, const py::array& ahigh,
+                               const py::array& kinds, const py::array& lows,
+                               const py::array& highs, const py::array& steps,
+                               const arr_f64& logw, int64_t w_num,
+                               double w_start, double w_step, double log_total,
+                               double prior_weight, bool consider_endpoints,
+                               bool magic_clip) {
+        check_fit_args("fused_draw_score", excl, n_above, logw);
+        if (table.ndim() != 2 || table.shape(1) != D_)
+            throw std::runtime_error("fused_draw_score: shape mismatch");
+        tpe_draw_py::HostDraw& H = draw_;
+        tpe_draw_py::draw(H, table, valid, below_rows, bw, u, q, alow, ahigh,
+                          kinds, lows, highs, steps, consider_endpoints,
+                          magic_clip, has_steps_, (size_t)FUSED_MAX_BELOW);
+        const int64_t S = (int64_t)H.S;
+        py::array_t<double> out(S);
+        py::array_t<double> x_raw = tpe_draw_py::copy_out(H.x_raw, H.S, H.D);
+        const double* h_out = score_candidates(
+            excl, n_above, H.x_kde.data(), H.xedges.data(), H.mus.data(),
+            H.sigmas.data(), static_cast<const double*>(bw.data()), S,
+            (int64_t)H.Kb(), logw, w_num, w_start, w_step, log_total,
+            prior_weight, consider_endpoints, magic_clip, nullptr);
+        memcpy(out.mutable_data(), h_out, (size_t)S * 8);
+        const size_t best = tpe_draw::argmax(h_out, (size_t)S);
+        return py::make_tuple(best, x_raw, out);
+    }
+
+  private:
+    // What the coefficients in coef_ were fitted from. They stay usable only
+    // while the table, the index, the domain and every fit argument are the
+    // same; every mutator of those clears `valid`.
+    struct PreparedFit {
+        bool valid = false;
+        int64_t n = 0, n_sorted = 0, Na = 0, w_num = 0;
+        double w_start = 0.0, w_step = 0.0, log_total = 0.0, prior_weight = 0.0;
+        bool consider_endpoints = false, magic_clip = false;
+        std::vector<int32_t> excl;
+        std::vector<double> logw;  // custom log-weights, empty for the ramp
+    };
+
+    void check_fit_args(const char* who, const arr_i32& excl, int64_t Na,
+                        const arr_f64& logw) const {
+        const std::string w(who);
+        if (!sorted_valid_) throw std::runtime_error(w + " before upload_sorted");
+        if (!domain_.ptr) throw std::runtime_error(w + " before set_domain");
+        if (has_categorical_)
+            throw std::runtime_error(w + ": categorical dims unsupported");
+        const int64_t E = excl.size();
+        const int64_t Nv = n_sorted_;
+        if (E > FUSED_MAX_EXCL || Na < 0 || Na > Nv || Na + E < Nv ||
+            (logw.size() > 0 && (int64_t)logw.size() != Na + 1))
+            throw std::runtime_error(w + ": shape mismatch");
+        // Strictly ascending in-table rows: keeps row - lower_bound(excl, row)
+        // inside [0, n_above) for every member row.
+        const int32_t* ex = excl.data();
+        for (int64_t e = 0; e < E; ++e)
+            if (ex[e] < 0 || ex[e] >= n_ || (e > 0 && ex[e] <= ex[e - 1]))
+                throw std::runtime_error(w + ": excl must be sorted table rows");
+    }
+
+    // Device half of a fused suggest on checked arguments: the fall-back fit,
+    // the packed upload, k_fused_score, k_fused_merge and the stream
+    // synchronise. Returns the merge's (3, S) result [ei | log g | log l] in
+    // pinned host memory, good until the next upload batch; lw_out, if given,
+    // receives the (K,) above log-weights.
+    const double* score_candidates(const arr_i32& excl, int64_t n_above,
+                                   const double* x, const double* xedges,
+                                   const double* bmu, const double* bsig,
+                                   const double* bw, int64_t S, int64_t Kb,
+                                   const arr_f64& logw, int64_t w_num,
+                                   double w_start, double w_step,
+                                   double log_total, double prior_weight,
+                                   bool consider_endpoints, bool magic_clip,
+                                   double* lw_out) {
+        const int64_t K = n_above + 1;
         hipStream_t st = g_ws.get_stream();
         g_ws.begin_uploads();
         if (!prepared_matches(excl, n_above, logw, w_num, w_start, w_step,
@@ -552,11 +657,11 @@ class TpeDeviceHistory {
                *d_part_s = s_part_s.in(base);
         {
             char* h = g_ws.stage(up_bytes, st);
-            memcpy(s_x.in(h), x.data(), n_x * 8);
-            memcpy(s_bmu.in(h), bmu.data(), n_b * 8);
-            memcpy(s_bsig.in(h), bsig.data(), n_b * 8);
-            memcpy(s_bw.in(h), bw.data(), (size_t)Kb * 8);
-            if (has_steps_) memcpy(s_xedges.in(h), xedges.data(), 2 * n_x * 8);
+            memcpy(s_x.in(h), x, n_x * 8);
+            memcpy(s_bmu.in(h), bmu, n_b * 8);
+            memcpy(s_bsig.in(h), bsig, n_b * 8);
+            memcpy(s_bw.in(h), bw, (size_t)Kb * 8);
+            if (has_steps_) memcpy(s_xedges.in(h), xedges, 2 * n_x * 8);
             HIP_CHECK(hipMemcpyAsync(base, h, up_bytes, hipMemcpyHostToDevice, st));
         }
 
@@ -581,54 +686,12 @@ class TpeDeviceHistory {
         hipLaunchKernelGGL(k_fused_merge, dim3((unsigned)S), dim3(64), 0, st,
                            d_part_m, d_part_s, n_as, n_bs, S,
                            const_cast<double*>(h_out));
-        if (return_parts) {
-            py::array_t<double> parts({(int64_t)3, S});
-            py::array_t<double> lw(K);
-            HIP_CHECK(hipMemcpyAsync(lw.mutable_data(), d_logw, (size_t)K * 8,
+        if (lw_out != nullptr)
+            HIP_CHECK(hipMemcpyAsync(lw_out, d_logw, (size_t)K * 8,
                                      hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            HIP_CHECK(hipGetLastError());
-            memcpy(parts.mutable_data(), h_out, 3 * (size_t)S * 8);
-            return py::make_tuple(parts, lw);
-        }
-        py::array_t<double> out(S);
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipGetLastError());
-        memcpy(out.mutable_data(), h_out, (size_t)S * 8);
-        return out;
-    }
-
-  private:
-    // What the coefficients in coef_ were fitted from. They stay usable only
-    // while the table, the index, the domain and every fit argument are the
-    // same; every mutator of those clears `valid`.
-    struct PreparedFit {
-        bool valid = false;
-        int64_t n = 0, n_sorted = 0, Na = 0, w_num = 0;
-        double w_start = 0.0, w_step = 0.0, log_total = 0.0, prior_weight = 0.0;
-        bool consider_endpoints = false, magic_clip = false;
-        std::vector<int32_t> excl;
-        std::vector<double> logw;  // custom log-weights, empty for the ramp
-    };
-
-    void check_fit_args(const char* who, const arr_i32& excl, int64_t Na,
-                        const arr_f64& logw) const {
-        const std::string w(who);
-        if (!sorted_valid_) throw std::runtime_error(w + " before upload_sorted");
-        if (!domain_.ptr) throw std::runtime_error(w + " before set_domain");
-        if (has_categorical_)
-            throw std::runtime_error(w + ": categorical dims unsupported");
-        const int64_t E = excl.size();
-        const int64_t Nv = n_sorted_;
-        if (E > FUSED_MAX_EXCL || Na < 0 || Na > Nv || Na + E < Nv ||
-            (logw.size() > 0 && (int64_t)logw.size() != Na + 1))
-            throw std::runtime_error(w + ": shape mismatch");
-        // Strictly ascending in-table rows: keeps row - lower_bound(excl, row)
-        // inside [0, n_above) for every member row.
-        const int32_t* ex = excl.data();
-        for (int64_t e = 0; e < E; ++e)
-            if (ex[e] < 0 || ex[e] >= n_ || (e > 0 && ex[e] <= ex[e - 1]))
-                throw std::runtime_error(w + ": excl must be sorted table rows");
+        return h_out;
     }
 
     // Bit-wise comparisons throughout: equal arguments give the same fit.
@@ -747,4 +810,5 @@ class TpeDeviceHistory {
     // point), grown geometrically.
     DeviceBuffer<char> coef_;
     PreparedFit prep_;
+    tpe_draw_py::HostDraw draw_;  // host half of fused_draw_score
 };

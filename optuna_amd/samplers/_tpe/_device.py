@@ -1,6 +1,6 @@
 """Device dispatch for the TPE hot path (K1 fit + K2 mixture log-pdf on gfx950).
 
-Three device modes:
+Device modes:
 
 * **Resident history** (the fast path): each (study, search-space) keeps a
   ``TpeDeviceHistory`` whose parameter table lives in HBM and grows append-only
@@ -24,6 +24,22 @@ Three device modes:
   numpy arithmetic of `parzen.py` bit for bit; the truncated-normal quantile
   and the RNG calls stay in Python. Custom weights functions and
   `OPTUNA_AMD_TPE_NATIVE_BELOW=0` keep the Python estimator.
+* **Native draw route** (`native_draw`, the default on the fused path with the
+  native below route): everything behind `prepare_fused_resident` is one native
+  call, `TpeDeviceHistory.fused_draw_score`. The sampler makes the two RNG
+  calls of the draw (`random_sample(S)` for the kernel choice, `uniform` for
+  the (S, D) quantiles) and passes them on in a `DrawRequest`; the call gathers
+  the below rows from the host table, fits the below estimator, turns the
+  first draw into kernel indices as `RandomState.choice` does, evaluates the
+  truncated-normal quantile, maps the draws to the parameter domain, derives
+  the scoring inputs, runs the device half of the scoring call and returns the
+  index of the best candidate with the candidates. The quantile repeats
+  `_truncnorm_np.ppf` bit for bit: scipy's scalar `ndtr`, `log_ndtr` and
+  `ndtri_exp` are taken from the capsules of `scipy.special.cython_special`
+  and called per element, numpy's `log`, `log1p`, `exp` and `logaddexp` are
+  numpy's own ufuncs, called on packed arrays (`csrc/tpe_draw_host.h`,
+  `csrc/tpe_draw_bind.h`). `OPTUNA_AMD_TPE_NATIVE_DRAW=0`, an extension without
+  the entry or a scipy without those capsules keep the three-call route.
 * **Stateless scoring** (`kde_logpdf`): used by golden tests and the
   constant-liar path (whose observation set includes rows not in the table).
 
@@ -151,11 +167,15 @@ _UNRESOLVED = object()
 
 
 def native_below(cache: "_SpaceCache"):
-    """The extension's ``tpe_below_kernels`` when the native below route is on
-    for this space, else None (switched off, or no extension loaded). Resolved
-    once per space cache."""
+    """The extension's entry that fits the below estimator of a fused suggest
+    natively, or None (switched off, or no extension loaded): on the native
+    draw route (``native_draw``) the ``fused_draw_score`` of the space's
+    device history, which also draws and scores in the same call, otherwise
+    the host-only ``tpe_below_kernels``. Resolved once per space cache."""
     if not native_below_enabled():
         return None
+    if native_draw(cache):
+        return cache._native_draw_entry  # type: ignore[attr-defined]
     fn = getattr(cache, "_native_below", _UNRESOLVED)
     if fn is _UNRESOLVED:
         fn = getattr(_hip.get(), "tpe_below_kernels", None)
@@ -180,9 +200,7 @@ def draw_below_native(
     its ``_sample_array``: the same RNG calls in the same order, the same
     truncated-normal quantile, and a fit that repeats numpy's arithmetic.
     ``weights`` are that estimator's normalized mixture weights."""
-    ns = getattr(cache, "_numerical_space", None)
-    if ns is None:
-        ns = cache._numerical_space = _NumericalSpace.of(cache.dists)  # type: ignore[attr-defined]
+    ns = _numerical_space_of(cache)
     obs = cache.params[below_rows[cache.valid[below_rows]]]  # a fresh (n, D) copy
     if ns.is_log.any():
         obs[:, ns.is_log] = np.log(obs[:, ns.is_log])
@@ -194,6 +212,72 @@ def draw_below_native(
     x = _tn.ppf(q, a, b) * scale + loc
     _to_param_domain(x, ns.kinds, ns.lows, ns.highs, ns.steps)
     return x, mus, sigmas
+
+
+def native_draw_enabled() -> bool:
+    """``OPTUNA_AMD_TPE_NATIVE_DRAW=0`` keeps the draw, the scoring call and
+    the arg-max of a fused suggest as separate Python steps (A/B runs)."""
+    return os.environ.get("OPTUNA_AMD_TPE_NATIVE_DRAW", "1") != "0"
+
+
+def _draw_capsules() -> tuple | None:
+    """scipy's scalar ``ndtr``, ``log_ndtr`` and ``ndtri_exp`` on doubles, as
+    the capsules ``scipy.special.cython_special`` exports to other extension
+    modules; None when this scipy does not export them."""
+    try:
+        from scipy.special import cython_special
+
+        capi = cython_special.__pyx_capi__
+        return capi["__pyx_fuse_1ndtr"], capi["__pyx_fuse_1log_ndtr"], capi["ndtri_exp"]
+    except (ImportError, AttributeError, KeyError):
+        return None
+
+
+def _bind_native_draw(core) -> bool:
+    """Hands the capsules to the extension, which checks their signature
+    strings before it takes the pointers."""
+    bind = getattr(core, "tpe_draw_bind", None)
+    capsules = _draw_capsules() if bind is not None else None
+    return capsules is not None and bool(bind(*capsules))
+
+
+def native_draw(cache: "_SpaceCache") -> bool:
+    """Whether the native draw route is on for this space: ``native_below``
+    then gives the one-call entry, to be passed on in a ``DrawRequest``. Off
+    when switched off, while the space has no device mirror yet
+    (``prepare_fused_resident`` makes it), with an extension without
+    ``fused_draw_score``, or with a scipy whose scalar functions could not be
+    bound. Resolved once per space cache."""
+    if not native_draw_enabled():
+        return False
+    entry = getattr(cache, "_native_draw_entry", _UNRESOLVED)
+    if entry is _UNRESOLVED:
+        mirror = getattr(cache, "_device_mirror", None)
+        if mirror is None:
+            return False
+        entry = getattr(mirror._hist, "fused_draw_score", None)
+        if entry is not None and not _bind_native_draw(_hip.get()):
+            entry = None
+        cache._native_draw_entry = entry  # type: ignore[attr-defined]
+    return entry is not None
+
+
+def _numerical_space_of(cache: "_SpaceCache") -> _NumericalSpace:
+    ns = getattr(cache, "_numerical_space", None)
+    if ns is None:
+        ns = cache._numerical_space = _NumericalSpace.of(cache.dists)  # type: ignore[attr-defined]
+    return ns
+
+
+class DrawRequest(NamedTuple):
+    """Inputs of a fused suggest on the native draw route (``native_draw``)."""
+
+    below_rows: np.ndarray  # table rows of the below set
+    n_above: int  # valid rows outside the below set
+    below_weights: np.ndarray  # (Kb,) normalized, as for draw_below_native
+    u: np.ndarray  # (S,) random_sample draw of the kernel choice
+    q: np.ndarray  # (S, D) uniform draw of the quantile
+    entry: object  # what native_below gave: the history's fused_draw_score
 
 
 class FusedRequest(NamedTuple):
@@ -504,6 +588,57 @@ class _SpaceDeviceMirror:
         )
 
 
+    def draw_score_fused(
+        self,
+        cache: "_SpaceCache",
+        req: DrawRequest,
+        consider_endpoints: bool,
+        consider_magic_clip: bool,
+        prior_weight: float,
+    ) -> tuple[int, np.ndarray, np.ndarray]:
+        """Second half of a fused suggest on the native draw route, in one
+        native call: what ``draw_below_native`` (given its two RNG draws),
+        ``score_fused`` and the arg-max compute. Default weight ramp only.
+        Returns (best index, x_raw (S, D), (S,) acquisition values)."""
+        args = (
+            cache, req.below_rows, req.n_above, None, consider_endpoints,
+            consider_magic_clip, prior_weight,
+        )
+        if self._prepared is None or self._prepared[0] != self._suggest_key(*args):
+            self.prepare_fused(*args)
+        assert self._prepared is not None
+        fit_args, self._prepared = self._prepared[1], None
+        excl, n_above, logw, w_num, w_start, w_step, log_total = fit_args[:7]
+        ns = _numerical_space_of(cache)
+        # numpy's ufuncs run inside the call: log(0) and inf - inf of the
+        # quantile's edge cases are expected there, as in _truncnorm_np.
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return req.entry(  # type: ignore[operator]
+                excl,
+                n_above,
+                cache.params,
+                cache.valid,
+                np.ascontiguousarray(req.below_rows, dtype=np.int64),
+                req.below_weights,
+                req.u,
+                req.q,
+                ns.adapted_lows,
+                ns.adapted_highs,
+                ns.kinds,
+                ns.lows,
+                ns.highs,
+                ns.steps,
+                logw,
+                w_num,
+                w_start,
+                w_step,
+                log_total,
+                float(prior_weight),
+                consider_endpoints,
+                consider_magic_clip,
+            )
+
+
 def _mirror_of(cache: "_SpaceCache") -> _SpaceDeviceMirror:
     mirror = getattr(cache, "_device_mirror", None)
     if mirror is None:
@@ -543,8 +678,8 @@ def score_above_resident(
     prior_weight: float = 1.0,
     extras: np.ndarray | None = None,
     per_dim: bool = False,
-    fused: FusedRequest | None = None,
-) -> np.ndarray:
+    fused: FusedRequest | DrawRequest | None = None,
+) -> np.ndarray | tuple[int, np.ndarray, np.ndarray]:
     """log g(x) for candidates via the device-resident table (creates the mirror
     on first use; attached to the host space cache so lifetimes match).
     ``per_dim=True`` returns the (S, D) per-dimension 1-D mixture log-pdfs
@@ -552,8 +687,17 @@ def score_above_resident(
 
     With ``fused`` (see ``fused_eligible``) the call returns the acquisition
     values ``log l(x) - log g(x)`` instead; ``sel`` and ``samples`` are unused
-    and ``weights=None`` selects the default weight ramp, written on device."""
+    and ``weights=None`` selects the default weight ramp, written on device.
+
+    With a ``DrawRequest`` as ``fused`` (see ``native_draw``) the candidates
+    are drawn inside the same native call as well, and the call returns (index
+    of the best candidate, x_raw (S, D), (S,) acquisition values); default
+    ramp only."""
     mirror = _mirror_of(cache)
+    if isinstance(fused, DrawRequest):
+        return mirror.draw_score_fused(
+            cache, fused, consider_endpoints, consider_magic_clip, prior_weight
+        )
     if fused is not None:
         return mirror.score_fused(
             cache, fused, weights, consider_endpoints, consider_magic_clip, prior_weight

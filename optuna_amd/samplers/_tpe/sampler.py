@@ -520,12 +520,8 @@ class TPESampler(BaseSampler):
         )
         fused = fused and use_device
         fused_weights: np.ndarray | None = None
-        # Native below route: the below estimator of a fused suggest is fitted
-        # by one call into the extension instead of through numpy.
         below_native = None
         p = self._parzen_estimator_parameters
-        if fused and p.weights is default_weights and p.prior_weight >= 0:
-            below_native = _device.native_below(cache)
         if fused:
             # Everything the above-set fit needs is known here: launch it now
             # so it runs on the GPU under the host work below (the below
@@ -541,6 +537,12 @@ class TPESampler(BaseSampler):
                 p.consider_magic_clip,
                 prior_weight=p.prior_weight,
             )
+            # Native below route: the below estimator of a fused suggest is
+            # fitted by one call into the extension instead of through numpy
+            # (resolved behind the prepare call, which makes the device mirror
+            # the native draw route needs).
+            if p.weights is default_weights and p.prior_weight >= 0:
+                below_native = _device.native_below(cache)
 
         obs_above: dict[str, np.ndarray] = {}
         orders_above: dict[str, np.ndarray] | None = None
@@ -558,6 +560,30 @@ class TPESampler(BaseSampler):
             # Same draws, kernels and weights as the estimator below would
             # give; its scoring runs on device like that of any fused suggest.
             below_weights = self._below_weights(n_below_valid, study._is_multi_objective())
+            if self._n_ei_candidates > 0 and _device.native_draw(cache):
+                # Native draw route: the two RNG calls of the draw, in its
+                # order, then one native call up to the chosen candidate.
+                u = self._rng.rng.random_sample(self._n_ei_candidates)
+                q = self._rng.rng.uniform(
+                    low=0, high=1, size=(self._n_ei_candidates, len(cache.names))
+                )
+                best, x_below, _ = _device.score_above_resident(
+                    cache,
+                    None,
+                    None,
+                    None,
+                    p.consider_endpoints,
+                    p.consider_magic_clip,
+                    prior_weight=p.prior_weight,
+                    fused=_device.DrawRequest(
+                        below_rows, n_above, below_weights, u, q, below_native
+                    ),
+                )
+                chosen = dict(zip(cache.names, x_below[best].tolist()))
+                return {
+                    name: dist.to_external_repr(chosen[name])
+                    for name, dist in search_space.items()
+                }
             x_below, below_mus, below_sigmas = _device.draw_below_native(
                 below_native,
                 cache,

@@ -80,6 +80,8 @@ def main() -> None:
     optuna_amd.logging.set_verbosity(optuna_amd.logging.WARNING)
     times: dict[str, list[float]] = {
         "fused_score": [], "fused_prepare": [], "tpe_below_kernels": [], "sample_locked": [],
+        "fused_draw_score": [], "draw_below_native": [], "ppf": [], "score_fused": [],
+        "best_candidate": [],
     }
 
     def timed(fn, bucket: list[float]):
@@ -100,6 +102,16 @@ def main() -> None:
     _device._SpaceDeviceMirror.__init__ = init
     sampler_cls = optuna_amd.samplers.TPESampler
     sampler_cls._sample_locked = timed(sampler_cls._sample_locked, times["sample_locked"])
+    sampler_cls._best_candidate = staticmethod(
+        timed(sampler_cls._best_candidate, times["best_candidate"])
+    )
+    mirror_cls = _device._SpaceDeviceMirror
+    mirror_cls.score_fused = timed(mirror_cls.score_fused, times["score_fused"])
+    if hasattr(_device, "draw_below_native"):
+        _device._tn.ppf = timed(_device._tn.ppf, times["ppf"])
+        _device.draw_below_native = timed(
+            _device.draw_below_native, times["draw_below_native"]
+        )
     # A build from before the native below route has no such entry.
     orig_native = getattr(_device, "native_below", None)
     if orig_native is not None:
@@ -107,8 +119,8 @@ def main() -> None:
 
         def native_below(cache):
             fn = orig_native(cache)
-            if fn is None:
-                return None
+            if fn is None or getattr(fn, "__name__", "") != "tpe_below_kernels":
+                return fn  # none, or the draw route's entry (timed as fused_draw_score)
             if fn not in wrapped:
                 wrapped[fn] = timed(fn, times["tpe_below_kernels"])
             return wrapped[fn]
@@ -148,7 +160,8 @@ def main() -> None:
     for _ in range(args.steps):
         one_step()
     wall = time.perf_counter() - t0
-    assert len(times["fused_score"]) == args.steps, "the fused path was not taken"
+    n_scored = len(times["fused_score"]) + len(times["fused_draw_score"])
+    assert n_scored == args.steps, "the fused path was not taken"
 
     print(
         json.dumps(
@@ -162,6 +175,11 @@ def main() -> None:
                 "fused_prepare": _stats(times["fused_prepare"]),
                 "tpe_below_kernels": _stats(times["tpe_below_kernels"]),
                 "sample_locked": _stats(times["sample_locked"]),
+                "fused_draw_score": _stats(times["fused_draw_score"]),
+                "draw_below_native": _stats(times["draw_below_native"]),
+                "ppf": _stats(times["ppf"]),
+                "score_fused": _stats(times["score_fused"]),
+                "best_candidate": _stats(times["best_candidate"]),
             }
         ),
         flush=True,
