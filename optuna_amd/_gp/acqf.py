@@ -8,6 +8,7 @@ box decomposition, qLogEHVI :473, LogCEHVI :534). All math in fp64.
 from __future__ import annotations
 
 import math
+import os
 from abc import ABC, abstractmethod
 from typing import TYPE_CHECKING
 
@@ -485,6 +486,7 @@ class LogEHVI(BaseAcquisitionFunc):
         box_lower, box_upper = _get_boxes(Y_train, ref_point)
         self._box_lower = box_lower.to(dev)
         self._box_intervals = (box_upper - box_lower).clamp_min_(_EPS).to(dev)
+        self._fused = None
         super().__init__(
             np.mean([gpr.length_scales for gpr in gpr_list], axis=0), search_space, dev
         )
@@ -500,6 +502,96 @@ class LogEHVI(BaseAcquisitionFunc):
             non_dominated_box_lower_bounds=self._box_lower,
             non_dominated_box_intervals=self._box_intervals,
         )
+
+    # ---- fused K5 device path -------------------------------------------------------
+    # The torch evaluation above builds a (B, n_qmc, n_boxes, M) tensor and
+    # several temporaries of that size, plus their autograd copies. The fused
+    # session runs the M posteriors like the LogEI session (cross-covariance
+    # kernel + one rocBLAS dgemm each), then one kernel that streams the boxes
+    # and QMC samples of a candidate through LDS, and a closed-form input
+    # gradient. Taken for 2..4 objectives on device GPs with an explicit
+    # inverse and no running rows; everything else keeps the torch path.
+    # OPTUNA_AMD_GP_FUSED_EHVI=0 forces the torch path (A/B runs).
+
+    def _fused_session(self):
+        if self._fused is not None:
+            return self._fused or None
+        gprs = self._gpr_list
+        if (
+            self._device is None
+            or os.environ.get("OPTUNA_AMD_GP_FUSED_EHVI", "1") == "0"
+            or not 2 <= len(gprs) <= 4
+            or any(
+                g._cov_Y_Y_inv is None
+                or g._X_all is not g._X_train
+                or bool(g._is_categorical.any())
+                or g._X_train.shape[1] > 64
+                or g._X_train.shape != gprs[0]._X_train.shape
+                for g in gprs
+            )
+        ):
+            self._fused = False
+            return None
+        from optuna_amd import _hip
+
+        core = _hip.get()
+        if (
+            core is None
+            or not core.available()
+            or self._fixed_samples.shape[0] > core.GP_EHVI_MAX_Q
+        ):
+            self._fused = False
+            return None
+        # Our stream must not race torch's producers of these tensors.
+        torch.cuda.synchronize()
+        self._fused_refs = [
+            (
+                g._X_train.contiguous(),
+                g._cov_Y_Y_inv_Y.contiguous(),
+                g._cov_Y_Y_inv.contiguous(),
+                g.inverse_squared_lengthscales.contiguous(),
+            )
+            for g in gprs
+        ]
+        X0 = self._fused_refs[0][0]
+        self._fused = core.GpLogEhviSession(
+            [r[0].data_ptr() for r in self._fused_refs],
+            [r[1].data_ptr() for r in self._fused_refs],
+            [r[2].data_ptr() for r in self._fused_refs],
+            [r[3].data_ptr() for r in self._fused_refs],
+            [float(g.kernel_scale.item()) for g in gprs],
+            int(X0.shape[0]),
+            int(X0.shape[1]),
+            float(self._stabilizing_noise),
+            self._fixed_samples.cpu().numpy(),
+            self._box_lower.cpu().numpy(),
+            self._box_intervals.cpu().numpy(),
+        )
+        return self._fused
+
+    def eval_acqf_no_grad(self, x: np.ndarray) -> np.ndarray:
+        session = self._fused_session()
+        if session is not None:
+            x2 = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+            f, _ = session.eval(x2, with_grad=False)
+            return np.asarray(f) if x.ndim > 1 else np.asarray(f)[0]
+        return super().eval_acqf_no_grad(x)
+
+    def eval_acqf_batched_with_grad(self, x: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        session = self._fused_session()
+        if session is not None:
+            f, g = session.eval(np.ascontiguousarray(x, dtype=np.float64), with_grad=True)
+            return np.asarray(f), np.asarray(g)
+        return super().eval_acqf_batched_with_grad(x)
+
+    def eval_acqf_with_grad(self, x: np.ndarray) -> tuple[float, np.ndarray]:
+        session = self._fused_session()
+        if session is not None:
+            f, g = session.eval(
+                np.ascontiguousarray(x[None, :], dtype=np.float64), with_grad=True
+            )
+            return float(np.asarray(f)[0]), np.asarray(g)[0]
+        return super().eval_acqf_with_grad(x)
 
 
 class qLogEHVI(BaseAcquisitionFunc):

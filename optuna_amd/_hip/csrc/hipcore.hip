@@ -2,6 +2,7 @@
 // This file holds the includes and the Python bindings only.
 #include "hip_common.h"
 
+#include "gp_ehvi.h"
 #include "gp_logei.h"
 #include "mo_host.h"
 #include "mo_rank.h"
@@ -27,6 +28,21 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("eta_ptr"), py::arg("N"), py::arg("D"), py::arg("scale"),
              py::arg("stab_noise"), py::arg("threshold"))
         .def("eval", &GpLogEiSession::eval, py::arg("x"), py::arg("with_grad"));
+    py::class_<GpLogEhviSession>(m, "GpLogEhviSession")
+        .def(py::init<const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<double>&, int64_t, int64_t, double,
+                      const arr_f64&, const arr_f64&, const arr_f64&, int64_t>(),
+             py::arg("X_ptrs"), py::arg("alpha_ptrs"), py::arg("cinv_ptrs"),
+             py::arg("eta_ptrs"), py::arg("scales"), py::arg("N"), py::arg("D"),
+             py::arg("stab_noise"), py::arg("eps"), py::arg("lo"), py::arg("iv"),
+             py::arg("scratch_budget_bytes") = EHVI_SCRATCH_BUDGET_BYTES)
+        .def("n_chunks", &GpLogEhviSession::n_chunks, py::arg("B"),
+             py::arg("with_grad"))
+        .def("eval", &GpLogEhviSession::eval, py::arg("x"), py::arg("with_grad"));
+    m.attr("GP_EHVI_BOX_TILE") = py::int_(EHVI_BOX_TILE);
+    m.attr("GP_EHVI_MAX_Q") = py::int_(EHVI_MAX_Q);
+    m.attr("GP_EHVI_SCRATCH_BUDGET_BYTES") = py::int_(EHVI_SCRATCH_BUDGET_BYTES);
     py::class_<Hssp3dSession>(m, "Hssp3dSession")
         .def(py::init<const arr_f64&, double, double, double>(), py::arg("cand"),
              py::arg("ref_x"), py::arg("ref_y"), py::arg("ref_z"))
