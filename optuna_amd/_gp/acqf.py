@@ -387,7 +387,122 @@ class LCB(BaseAcquisitionFunc):
         return mean - torch.sqrt(self._beta * var)
 
 
-class LogCEI(BaseAcquisitionFunc):
+# ---- fused K5 device path of the constrained acquisitions ---------------------------
+# The feasibility term sum_c log Phi((mean_c - t_c) / sigma_c) runs on the device
+# as a GpConstraintSet over the LogPI members' GPs. Where the acquisition has an
+# objective term, the inner LogEI / LogEHVI session evaluates it and adds the
+# set's term on the device in the same native call; where it has none (no
+# feasible trial yet) the set is evaluated alone. An objective term whose own
+# session is unavailable keeps the whole acquisition on torch: it is never
+# evaluated half on each side. OPTUNA_AMD_GP_FUSED_CONSTRAINED=0 forces the torch
+# path (A/B runs).
+
+
+class _FusedConstrained:
+    """``eval(x, with_grad)`` over an objective session (or none) and a constraint set."""
+
+    def __init__(self, objective, constraints, refs) -> None:
+        self._objective = objective
+        self._constraints = constraints
+        self._refs = refs  # keeps the tensors behind the raw pointers alive
+
+    def eval(self, x: np.ndarray, with_grad: bool):
+        if self._objective is None:
+            return self._constraints.eval(x, with_grad)
+        return self._objective.eval(x, with_grad, constraints=self._constraints)
+
+
+def _fused_constrained_session(
+    device: "torch.device | None",
+    objective_acqf: "LogEI | LogEHVI | None",
+    objective_gprs: list[GPRegressor],
+    constraints_acqf_list: "list[LogPI]",
+) -> "_FusedConstrained | None":
+    """The fused evaluator of objective term + feasibility, or None for torch.
+
+    ``objective_acqf`` is None where there is legitimately no objective term.
+    """
+    c_gprs = [a._gpr for a in constraints_acqf_list]
+    shape = c_gprs[0]._X_train.shape
+    if (
+        device is None
+        or os.environ.get("OPTUNA_AMD_GP_FUSED_CONSTRAINED", "1") == "0"
+        or shape[1] > 64
+        or any(
+            g._cov_Y_Y_inv is None
+            or g._X_all is not g._X_train
+            or bool(g._is_categorical.any())
+            or g._X_train.shape != shape
+            for g in c_gprs
+        )
+    ):
+        return None
+    objective = None
+    if objective_acqf is not None:
+        if any(g._X_train.shape != shape for g in objective_gprs):
+            return None
+        objective = objective_acqf._fused_session()
+        if objective is None:
+            return None
+    from optuna_amd import _hip
+
+    core = _hip.get()
+    if core is None or not core.available() or len(c_gprs) > core.GP_FEAS_MAX_C:
+        return None
+    # Our stream must not race torch's producers of these tensors.
+    torch.cuda.synchronize()
+    refs = [
+        (
+            g._X_train.contiguous(),
+            g._cov_Y_Y_inv_Y.contiguous(),
+            g._cov_Y_Y_inv.contiguous(),
+            g.inverse_squared_lengthscales.contiguous(),
+        )
+        for g in c_gprs
+    ]
+    constraints = core.GpConstraintSet(
+        [r[0].data_ptr() for r in refs],
+        [r[1].data_ptr() for r in refs],
+        [r[2].data_ptr() for r in refs],
+        [r[3].data_ptr() for r in refs],
+        [float(g.kernel_scale.item()) for g in c_gprs],
+        [float(a._threshold) for a in constraints_acqf_list],
+        int(shape[0]),
+        int(shape[1]),
+        float(constraints_acqf_list[0]._stabilizing_noise),
+    )
+    return _FusedConstrained(objective, constraints, refs)
+
+
+class _FusedEntryPoints:
+    """The three numpy entry points over ``_fused_session()``; torch where it is None."""
+
+    def eval_acqf_no_grad(self, x: np.ndarray) -> np.ndarray:
+        session = self._fused_session()
+        if session is not None:
+            x2 = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+            f, _ = session.eval(x2, with_grad=False)
+            return np.asarray(f) if x.ndim > 1 else np.asarray(f)[0]
+        return super().eval_acqf_no_grad(x)
+
+    def eval_acqf_batched_with_grad(self, x: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        session = self._fused_session()
+        if session is not None:
+            f, g = session.eval(np.ascontiguousarray(x, dtype=np.float64), with_grad=True)
+            return np.asarray(f), np.asarray(g)
+        return super().eval_acqf_batched_with_grad(x)
+
+    def eval_acqf_with_grad(self, x: np.ndarray) -> tuple[float, np.ndarray]:
+        session = self._fused_session()
+        if session is not None:
+            f, g = session.eval(
+                np.ascontiguousarray(x[None, :], dtype=np.float64), with_grad=True
+            )
+            return float(np.asarray(f)[0]), np.asarray(g)[0]
+        return super().eval_acqf_with_grad(x)
+
+
+class LogCEI(_FusedEntryPoints, BaseAcquisitionFunc):
     """log(EI × ∏ feasibility-PI of each constraint)."""
 
     def __init__(
@@ -407,12 +522,28 @@ class LogCEI(BaseAcquisitionFunc):
             LogPI(c_gpr, search_space, c_threshold, None, stabilizing_noise)
             for c_gpr, c_threshold in zip(constraints_gpr_list, constraints_threshold_list)
         ]
+        self._fused = None
         super().__init__(gpr.length_scales, search_space, gpr.device)
 
     def eval_acqf(self, x: "torch.Tensor") -> "torch.Tensor":
         return self._acqf.eval_acqf(x) + sum(
             acqf.eval_acqf(x) for acqf in self._constraints_acqf_list
         )
+
+    def _fused_session(self):
+        if self._fused is None:
+            # A threshold of -inf (no feasible trial yet) makes the EI term zero.
+            has_objective = not np.isneginf(self._acqf._threshold)
+            self._fused = (
+                _fused_constrained_session(
+                    self._device,
+                    self._acqf if has_objective else None,
+                    [self._acqf._gpr],
+                    self._constraints_acqf_list,
+                )
+                or False
+            )
+        return self._fused or None
 
 
 class qLogCEI(BaseAcquisitionFunc):
@@ -646,7 +777,7 @@ class qLogEHVI(BaseAcquisitionFunc):
         return torch.special.logsumexp(log_utils, dim=-1) - math.log(log_utils.shape[-1])
 
 
-class LogCEHVI(BaseAcquisitionFunc):
+class LogCEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
     """EHVI over feasible observations × feasibility-PI of each constraint."""
 
     def __init__(
@@ -688,11 +819,26 @@ class LogCEHVI(BaseAcquisitionFunc):
             )
             for c_gpr, c_threshold in zip(constraints_gpr_list, constraints_threshold_list)
         ]
+        self._fused = None
         super().__init__(
             np.mean([gpr.length_scales for gpr in gpr_list], axis=0),
             search_space,
             gpr_list[0].device,
         )
+
+    def _fused_session(self):
+        if self._fused is None:
+            # Y_feasible=None (no feasible trial yet) leaves the feasibility alone.
+            self._fused = (
+                _fused_constrained_session(
+                    self._device,
+                    self._acqf,
+                    self._acqf._gpr_list if self._acqf is not None else [],
+                    self._constraints_acqf_list,
+                )
+                or False
+            )
+        return self._fused or None
 
     def eval_acqf(self, x: "torch.Tensor") -> "torch.Tensor":
         feasibility = sum(acqf.eval_acqf(x) for acqf in self._constraints_acqf_list)

@@ -360,9 +360,14 @@ class GpLogEhviSession {
         return (int)std::clamp<int64_t>((EHVI_TARGET_BLOCKS + bc - 1) / bc, 1, tiles);
     }
 
-    py::tuple eval(const arr_f64& x, bool with_grad) {
+    // With a constraint set the feasibility term and its gradient are added
+    // on the device, chunk by chunk in the first K / MP / V set once the
+    // objectives are done with it, before the one copy back.
+    py::tuple eval(const arr_f64& x, bool with_grad,
+                   const GpConstraintSet* constraints = nullptr) {
         if (x.ndim() != 2 || x.shape(1) != D_)
             throw std::runtime_error("eval: dim mismatch");
+        if (constraints) feas_check_shape(constraints, N_, D_);
         const int64_t B = x.shape(0);
         py::array_t<double> f(B);
         py::array_t<double> g;
@@ -386,14 +391,16 @@ class GpLogEhviSession {
                    s_g = L.add<double>(with_grad ? nBD : 0),
                    s_K = L.add<double>(nK * n_sets),
                    s_MP = L.add<double>(nK * n_sets),
-                   s_V = L.add<double>(nK * n_sets);
+                   s_V = L.add<double>(nK * n_sets),
+                   s_cpart = L.add<double>(
+                       constraints ? feas_part_doubles(constraints, rows, with_grad) : 0);
         char* base = g_ws.ensure_bytes(L.bytes());
         double *d_x = s_x.in(base), *d_mean = s_mean.in(base),
                *d_sd = s_sd.in(base), *d_dsd = s_dsd.in(base),
                *d_f = s_f.in(base), *d_part = s_part.in(base),
                *d_wm = s_wm.in(base), *d_wv = s_wv.in(base),
                *d_g = s_g.in(base), *d_K = s_K.in(base), *d_MP = s_MP.in(base),
-               *d_V = s_V.in(base);
+               *d_V = s_V.in(base), *d_cpart = s_cpart.in(base);
         g_ws.begin_uploads();
         g_ws.h2d(d_x, x.data(), nBD * 8, st);
 
@@ -435,6 +442,10 @@ class GpLogEhviSession {
                                    dim3(EHVI_BLOCK), 0, st, ga, M_,
                                    d_wm + b0 * M_, d_wv + b0 * M_, xc, N_,
                                    (int)D_, d_g + b0 * D_);
+            if (constraints)
+                feas_enqueue_add(constraints, st, blas, xc, bc, with_grad, d_K, d_MP,
+                                 d_V, d_cpart, d_f + b0,
+                                 with_grad ? d_g + b0 * D_ : nullptr);
         }
         HIP_CHECK(hipMemcpyAsync(f.mutable_data(), d_f, B * 8,
                                  hipMemcpyDeviceToHost, st));

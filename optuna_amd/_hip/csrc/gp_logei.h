@@ -163,6 +163,21 @@ __global__ void k_gp_logei_final(const double* __restrict__ K,      // (B, N)
     }
 }
 
+// The feasibility term of the constrained acquisitions (gp_feasibility.h),
+// which the sessions add to their own result on the device when handed a
+// constraint set. With no set (nullptr) nothing below does anything.
+class GpConstraintSet;
+// Throws unless the set was built for the same (N, D).
+static void feas_check_shape(const GpConstraintSet* cs, int64_t N, int64_t D);
+// Doubles of partial records for chunks of at most `rows` candidates.
+static size_t feas_part_doubles(const GpConstraintSet* cs, int64_t rows, bool with_grad);
+// Enqueue f += sum_c log Phi(z_c), g += its gradient for the bc candidates xc;
+// K / MP / V are (bc, N) scratch the caller is done with.
+static void feas_enqueue_add(const GpConstraintSet* cs, hipStream_t st,
+                             rocblas_handle blas, const double* xc, int64_t bc,
+                             bool with_grad, double* K, double* MP, double* V,
+                             double* part, double* f, double* g);
+
 // Session over torch-owned device tensors (raw pointers; same HIP context).
 // Built once per fitted GP; evaluations upload only the (B, D) candidates.
 class GpLogEiSession {
@@ -178,18 +193,30 @@ class GpLogEiSession {
         if (D > 64) throw std::runtime_error("GpLogEiSession: D > 64");
     }
 
-    py::tuple eval(const arr_f64& x, bool with_grad) {
+    // With a constraint set the feasibility term and its gradient are added
+    // on the device, in the (B, N) regions the log-EI kernels are done with,
+    // before the one copy back.
+    py::tuple eval(const arr_f64& x, bool with_grad,
+                   const GpConstraintSet* constraints = nullptr) {
         const int64_t B = x.shape(0);
         if (x.shape(1) != D_) throw std::runtime_error("eval: dim mismatch");
+        if (constraints) {
+            feas_check_shape(constraints, N_, D_);
+            // 65535 is the grid's y extent in k_gp_cross_cov.
+            if (B > 65535) throw std::runtime_error("eval: more than 65535 candidates");
+        }
         hipStream_t st = g_ws.get_stream();
         const size_t nK = (size_t)B * N_;
         WsLayout L;
         const auto s_K = L.add<double>(nK), s_MP = L.add<double>(nK),
                    s_V = L.add<double>(nK), s_x = L.add<double>((size_t)B * D_),
-                   s_f = L.add<double>(B), s_g = L.add<double>((size_t)B * D_);
+                   s_f = L.add<double>(B), s_g = L.add<double>((size_t)B * D_),
+                   s_part = L.add<double>(
+                       constraints ? feas_part_doubles(constraints, B, with_grad) : 0);
         char* base = g_ws.ensure_bytes(L.bytes());
         double *d_K = s_K.in(base), *d_MP = s_MP.in(base), *d_V = s_V.in(base),
-               *d_x = s_x.in(base), *d_f = s_f.in(base), *d_g = s_g.in(base);
+               *d_x = s_x.in(base), *d_f = s_f.in(base), *d_g = s_g.in(base),
+               *d_part = s_part.in(base);
         g_ws.begin_uploads();
         g_ws.h2d(d_x, x.data(), (size_t)B * D_ * 8, st);
         {
@@ -213,6 +240,9 @@ class GpLogEiSession {
                            st, d_K, d_MP, d_V, alpha_, X_, eta_, d_x, scale_,
                            stab_, thr_, N_, D_, d_f,
                            with_grad ? d_g : nullptr);
+        if (constraints && B > 0)
+            feas_enqueue_add(constraints, st, get_blas(st), d_x, B, with_grad, d_K,
+                             d_MP, d_V, d_part, d_f, with_grad ? d_g : nullptr);
         py::array_t<double> f(B);
         HIP_CHECK(hipMemcpyAsync(f.mutable_data(), d_f, B * 8,
                                  hipMemcpyDeviceToHost, st));

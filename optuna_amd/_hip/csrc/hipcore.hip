@@ -3,6 +3,7 @@
 #include "hip_common.h"
 
 #include "gp_ehvi.h"
+#include "gp_feasibility.h"
 #include "gp_logei.h"
 #include "mo_host.h"
 #include "mo_rank.h"
@@ -21,13 +22,28 @@ PYBIND11_MODULE(_hipcore, m) {
           py::arg("n_below"));
     m.def("hv3d", &hv3d, py::arg("pts"), py::arg("ref_x"), py::arg("ref_y"),
           py::arg("ref_z"));
+    py::class_<GpConstraintSet>(m, "GpConstraintSet")
+        .def(py::init<const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<double>&, const std::vector<double>&,
+                      int64_t, int64_t, double, int64_t>(),
+             py::arg("X_ptrs"), py::arg("alpha_ptrs"), py::arg("cinv_ptrs"),
+             py::arg("eta_ptrs"), py::arg("scales"), py::arg("thresholds"),
+             py::arg("N"), py::arg("D"), py::arg("stab_noise"),
+             py::arg("scratch_budget_bytes") = EHVI_SCRATCH_BUDGET_BYTES)
+        .def("n_chunks", &GpConstraintSet::n_chunks, py::arg("B"),
+             py::arg("with_grad"))
+        .def("n_splits", &GpConstraintSet::n_splits, py::arg("bc"))
+        .def("eval", &GpConstraintSet::eval, py::arg("x"), py::arg("with_grad"));
+    m.attr("GP_FEAS_MAX_C") = py::int_(FEAS_MAX_C);
     py::class_<GpLogEiSession>(m, "GpLogEiSession")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                       double, double, double>(),
              py::arg("X_ptr"), py::arg("alpha_ptr"), py::arg("cinv_ptr"),
              py::arg("eta_ptr"), py::arg("N"), py::arg("D"), py::arg("scale"),
              py::arg("stab_noise"), py::arg("threshold"))
-        .def("eval", &GpLogEiSession::eval, py::arg("x"), py::arg("with_grad"));
+        .def("eval", &GpLogEiSession::eval, py::arg("x"), py::arg("with_grad"),
+             py::arg("constraints") = py::none());
     py::class_<GpLogEhviSession>(m, "GpLogEhviSession")
         .def(py::init<const std::vector<int64_t>&, const std::vector<int64_t>&,
                       const std::vector<int64_t>&, const std::vector<int64_t>&,
@@ -39,7 +55,8 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("scratch_budget_bytes") = EHVI_SCRATCH_BUDGET_BYTES)
         .def("n_chunks", &GpLogEhviSession::n_chunks, py::arg("B"),
              py::arg("with_grad"))
-        .def("eval", &GpLogEhviSession::eval, py::arg("x"), py::arg("with_grad"));
+        .def("eval", &GpLogEhviSession::eval, py::arg("x"), py::arg("with_grad"),
+             py::arg("constraints") = py::none());
     m.attr("GP_EHVI_BOX_TILE") = py::int_(EHVI_BOX_TILE);
     m.attr("GP_EHVI_MAX_Q") = py::int_(EHVI_MAX_Q);
     m.attr("GP_EHVI_SCRATCH_BUDGET_BYTES") = py::int_(EHVI_SCRATCH_BUDGET_BYTES);
