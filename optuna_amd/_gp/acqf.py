@@ -188,73 +188,58 @@ class BaseAcquisitionFunc(ABC):
         )
 
 
-class LogEI(BaseAcquisitionFunc):
-    def __init__(
-        self,
-        gpr: GPRegressor,
-        search_space: "SearchSpace",
-        threshold: float,
-        stabilizing_noise: float = 1e-12,
-    ) -> None:
-        self._gpr = gpr
-        self._stabilizing_noise = stabilizing_noise
-        self._threshold = threshold
-        self._fused = None
-        super().__init__(gpr.length_scales, search_space, gpr.device)
+# ---- fused K5 device path: what its four users share --------------------------------
 
-    def eval_acqf(self, x: "torch.Tensor") -> "torch.Tensor":
-        if np.isneginf(self._threshold):
-            return torch.zeros(x.shape[:-1], dtype=torch.float64, device=x.device)
-        mean, var = self._gpr.posterior(x)
-        return logei(mean=mean, var=var + self._stabilizing_noise, f0=self._threshold)
 
-    # ---- fused K5 device path -------------------------------------------------------
-    # On the MI355X the torch evaluation costs ~50 kernel launches per call
-    # (posterior GEMMs + erfc branches + autograd); the K5 kernel computes the
-    # cross-covariance, one rocBLAS dgemm against the resident explicit
-    # inverse, and the tail-stable log-EI with its CLOSED-FORM gradient — four
-    # launches total, operating directly on the torch-owned device tensors.
+def _fused_core():
+    """The loaded HIP extension with a device behind it, or None."""
+    from optuna_amd import _hip
+
+    core = _hip.get()
+    return core if core is not None and core.available() else None
+
+
+def _device_ready(gpr: GPRegressor) -> bool:
+    """Whether a native session can take ``gpr`` as raw pointers: an explicit
+    inverse, no running rows, no categorical dimension and D <= 64."""
+    return (
+        gpr._cov_Y_Y_inv is not None
+        and gpr._X_all is gpr._X_train
+        and not bool(gpr._is_categorical.any())
+        and gpr._X_train.shape[1] <= 64
+    )
+
+
+def _device_tensors(gprs: list[GPRegressor]) -> "list[list[torch.Tensor]]":
+    """The contiguous X, alpha, inverse and eta tensors of ``gprs``, one list each.
+
+    Whoever takes their ``data_ptr()`` keeps the lists alive with the session.
+    """
+    # Our stream must not race torch's producers of these tensors.
+    torch.cuda.synchronize()
+    return [
+        [g._X_train.contiguous() for g in gprs],
+        [g._cov_Y_Y_inv_Y.contiguous() for g in gprs],
+        [g._cov_Y_Y_inv.contiguous() for g in gprs],
+        [g.inverse_squared_lengthscales.contiguous() for g in gprs],
+    ]
+
+
+def _pointers(tensors: "list[list[torch.Tensor]]") -> list[list[int]]:
+    return [[t.data_ptr() for t in ts] for ts in tensors]
+
+
+class _FusedEntryPoints:
+    """The three numpy entry points over ``_fused_session()``; torch where it is None.
+
+    ``_build_fused_session()`` of the class decides once per acquisition: a native
+    session (anything with ``eval(x, with_grad)``) or None. It leaves the tensors
+    behind the session's raw pointers in ``self._fused_refs``.
+    """
 
     def _fused_session(self):
-        if self._fused is not None:
-            return self._fused or None
-        gpr = self._gpr
-        if (
-            self._device is None
-            or np.isneginf(self._threshold)
-            or gpr._cov_Y_Y_inv is None
-            or gpr._X_all is not gpr._X_train
-            or bool(gpr._is_categorical.any())
-            or gpr._X_train.shape[1] > 64
-        ):
-            self._fused = False
-            return None
-        from optuna_amd import _hip
-
-        core = _hip.get()
-        if core is None or not core.available():
-            self._fused = False
-            return None
-        # Our stream must not race torch's producers of these tensors.
-        torch.cuda.synchronize()
-        self._fused_refs = (
-            gpr._X_train.contiguous(),
-            gpr._cov_Y_Y_inv_Y.contiguous(),
-            gpr._cov_Y_Y_inv.contiguous(),
-            gpr.inverse_squared_lengthscales.contiguous(),
-        )
-        X, alpha, cinv, eta = self._fused_refs
-        self._fused = core.GpLogEiSession(
-            X.data_ptr(),
-            alpha.data_ptr(),
-            cinv.data_ptr(),
-            eta.data_ptr(),
-            int(X.shape[0]),
-            int(X.shape[1]),
-            float(self._gpr.kernel_scale.item()),
-            float(self._stabilizing_noise),
-            float(self._threshold),
-        )
+        if "_fused" not in self.__dict__:
+            self._fused = self._build_fused_session()
         return self._fused
 
     def eval_acqf_no_grad(self, x: np.ndarray) -> np.ndarray:
@@ -280,6 +265,54 @@ class LogEI(BaseAcquisitionFunc):
             )
             return float(np.asarray(f)[0]), np.asarray(g)[0]
         return super().eval_acqf_with_grad(x)
+
+
+class LogEI(_FusedEntryPoints, BaseAcquisitionFunc):
+    def __init__(
+        self,
+        gpr: GPRegressor,
+        search_space: "SearchSpace",
+        threshold: float,
+        stabilizing_noise: float = 1e-12,
+    ) -> None:
+        self._gpr = gpr
+        self._stabilizing_noise = stabilizing_noise
+        self._threshold = threshold
+        super().__init__(gpr.length_scales, search_space, gpr.device)
+
+    def eval_acqf(self, x: "torch.Tensor") -> "torch.Tensor":
+        if np.isneginf(self._threshold):
+            return torch.zeros(x.shape[:-1], dtype=torch.float64, device=x.device)
+        mean, var = self._gpr.posterior(x)
+        return logei(mean=mean, var=var + self._stabilizing_noise, f0=self._threshold)
+
+    # ---- fused K5 device path -------------------------------------------------------
+    # On the MI355X the torch evaluation costs ~50 kernel launches per call
+    # (posterior GEMMs + erfc branches + autograd); the K5 kernel computes the
+    # cross-covariance, one rocBLAS dgemm against the resident explicit
+    # inverse, and the tail-stable log-EI with its CLOSED-FORM gradient — four
+    # launches total, operating directly on the torch-owned device tensors.
+
+    def _build_fused_session(self):
+        gpr = self._gpr
+        if self._device is None or np.isneginf(self._threshold) or not _device_ready(gpr):
+            return None
+        core = _fused_core()
+        if core is None:
+            return None
+        self._fused_refs = _device_tensors([gpr])
+        (X_ptr,), (alpha_ptr,), (cinv_ptr,), (eta_ptr,) = _pointers(self._fused_refs)
+        return core.GpLogEiSession(
+            X_ptr,
+            alpha_ptr,
+            cinv_ptr,
+            eta_ptr,
+            int(gpr._X_train.shape[0]),
+            int(gpr._X_train.shape[1]),
+            float(gpr.kernel_scale.item()),
+            float(self._stabilizing_noise),
+            float(self._threshold),
+        )
 
 
 class qLogEI(BaseAcquisitionFunc):
@@ -401,10 +434,9 @@ class LCB(BaseAcquisitionFunc):
 class _FusedConstrained:
     """``eval(x, with_grad)`` over an objective session (or none) and a constraint set."""
 
-    def __init__(self, objective, constraints, refs) -> None:
+    def __init__(self, objective, constraints) -> None:
         self._objective = objective
         self._constraints = constraints
-        self._refs = refs  # keeps the tensors behind the raw pointers alive
 
     def eval(self, x: np.ndarray, with_grad: bool):
         if self._objective is None:
@@ -413,28 +445,21 @@ class _FusedConstrained:
 
 
 def _fused_constrained_session(
-    device: "torch.device | None",
+    acqf: "LogCEI | LogCEHVI",
     objective_acqf: "LogEI | LogEHVI | None",
     objective_gprs: list[GPRegressor],
-    constraints_acqf_list: "list[LogPI]",
 ) -> "_FusedConstrained | None":
-    """The fused evaluator of objective term + feasibility, or None for torch.
+    """The fused evaluator of objective term + feasibility of ``acqf``, or None for torch.
 
     ``objective_acqf`` is None where there is legitimately no objective term.
     """
+    constraints_acqf_list = acqf._constraints_acqf_list
     c_gprs = [a._gpr for a in constraints_acqf_list]
     shape = c_gprs[0]._X_train.shape
     if (
-        device is None
+        acqf._device is None
         or os.environ.get("OPTUNA_AMD_GP_FUSED_CONSTRAINED", "1") == "0"
-        or shape[1] > 64
-        or any(
-            g._cov_Y_Y_inv is None
-            or g._X_all is not g._X_train
-            or bool(g._is_categorical.any())
-            or g._X_train.shape != shape
-            for g in c_gprs
-        )
+        or any(not _device_ready(g) or g._X_train.shape != shape for g in c_gprs)
     ):
         return None
     objective = None
@@ -444,62 +469,19 @@ def _fused_constrained_session(
         objective = objective_acqf._fused_session()
         if objective is None:
             return None
-    from optuna_amd import _hip
-
-    core = _hip.get()
-    if core is None or not core.available() or len(c_gprs) > core.GP_FEAS_MAX_C:
+    core = _fused_core()
+    if core is None or len(c_gprs) > core.GP_FEAS_MAX_C:
         return None
-    # Our stream must not race torch's producers of these tensors.
-    torch.cuda.synchronize()
-    refs = [
-        (
-            g._X_train.contiguous(),
-            g._cov_Y_Y_inv_Y.contiguous(),
-            g._cov_Y_Y_inv.contiguous(),
-            g.inverse_squared_lengthscales.contiguous(),
-        )
-        for g in c_gprs
-    ]
+    acqf._fused_refs = _device_tensors(c_gprs)
     constraints = core.GpConstraintSet(
-        [r[0].data_ptr() for r in refs],
-        [r[1].data_ptr() for r in refs],
-        [r[2].data_ptr() for r in refs],
-        [r[3].data_ptr() for r in refs],
+        *_pointers(acqf._fused_refs),
         [float(g.kernel_scale.item()) for g in c_gprs],
         [float(a._threshold) for a in constraints_acqf_list],
         int(shape[0]),
         int(shape[1]),
         float(constraints_acqf_list[0]._stabilizing_noise),
     )
-    return _FusedConstrained(objective, constraints, refs)
-
-
-class _FusedEntryPoints:
-    """The three numpy entry points over ``_fused_session()``; torch where it is None."""
-
-    def eval_acqf_no_grad(self, x: np.ndarray) -> np.ndarray:
-        session = self._fused_session()
-        if session is not None:
-            x2 = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-            f, _ = session.eval(x2, with_grad=False)
-            return np.asarray(f) if x.ndim > 1 else np.asarray(f)[0]
-        return super().eval_acqf_no_grad(x)
-
-    def eval_acqf_batched_with_grad(self, x: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
-        session = self._fused_session()
-        if session is not None:
-            f, g = session.eval(np.ascontiguousarray(x, dtype=np.float64), with_grad=True)
-            return np.asarray(f), np.asarray(g)
-        return super().eval_acqf_batched_with_grad(x)
-
-    def eval_acqf_with_grad(self, x: np.ndarray) -> tuple[float, np.ndarray]:
-        session = self._fused_session()
-        if session is not None:
-            f, g = session.eval(
-                np.ascontiguousarray(x[None, :], dtype=np.float64), with_grad=True
-            )
-            return float(np.asarray(f)[0]), np.asarray(g)[0]
-        return super().eval_acqf_with_grad(x)
+    return _FusedConstrained(objective, constraints)
 
 
 class LogCEI(_FusedEntryPoints, BaseAcquisitionFunc):
@@ -522,7 +504,6 @@ class LogCEI(_FusedEntryPoints, BaseAcquisitionFunc):
             LogPI(c_gpr, search_space, c_threshold, None, stabilizing_noise)
             for c_gpr, c_threshold in zip(constraints_gpr_list, constraints_threshold_list)
         ]
-        self._fused = None
         super().__init__(gpr.length_scales, search_space, gpr.device)
 
     def eval_acqf(self, x: "torch.Tensor") -> "torch.Tensor":
@@ -530,20 +511,12 @@ class LogCEI(_FusedEntryPoints, BaseAcquisitionFunc):
             acqf.eval_acqf(x) for acqf in self._constraints_acqf_list
         )
 
-    def _fused_session(self):
-        if self._fused is None:
-            # A threshold of -inf (no feasible trial yet) makes the EI term zero.
-            has_objective = not np.isneginf(self._acqf._threshold)
-            self._fused = (
-                _fused_constrained_session(
-                    self._device,
-                    self._acqf if has_objective else None,
-                    [self._acqf._gpr],
-                    self._constraints_acqf_list,
-                )
-                or False
-            )
-        return self._fused or None
+    def _build_fused_session(self):
+        # A threshold of -inf (no feasible trial yet) makes the EI term zero.
+        has_objective = not np.isneginf(self._acqf._threshold)
+        return _fused_constrained_session(
+            self, self._acqf if has_objective else None, [self._acqf._gpr]
+        )
 
 
 class qLogCEI(BaseAcquisitionFunc):
@@ -589,7 +562,7 @@ class qLogCEI(BaseAcquisitionFunc):
         return _mean_max_log_utility(log_feasible_improvement)
 
 
-class LogEHVI(BaseAcquisitionFunc):
+class LogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
     def __init__(
         self,
         gpr_list: list[GPRegressor],
@@ -617,7 +590,6 @@ class LogEHVI(BaseAcquisitionFunc):
         box_lower, box_upper = _get_boxes(Y_train, ref_point)
         self._box_lower = box_lower.to(dev)
         self._box_intervals = (box_upper - box_lower).clamp_min_(_EPS).to(dev)
-        self._fused = None
         super().__init__(
             np.mean([gpr.length_scales for gpr in gpr_list], axis=0), search_space, dev
         )
@@ -644,85 +616,30 @@ class LogEHVI(BaseAcquisitionFunc):
     # inverse and no running rows; everything else keeps the torch path.
     # OPTUNA_AMD_GP_FUSED_EHVI=0 forces the torch path (A/B runs).
 
-    def _fused_session(self):
-        if self._fused is not None:
-            return self._fused or None
+    def _build_fused_session(self):
         gprs = self._gpr_list
+        shape = gprs[0]._X_train.shape
         if (
             self._device is None
             or os.environ.get("OPTUNA_AMD_GP_FUSED_EHVI", "1") == "0"
             or not 2 <= len(gprs) <= 4
-            or any(
-                g._cov_Y_Y_inv is None
-                or g._X_all is not g._X_train
-                or bool(g._is_categorical.any())
-                or g._X_train.shape[1] > 64
-                or g._X_train.shape != gprs[0]._X_train.shape
-                for g in gprs
-            )
+            or any(not _device_ready(g) or g._X_train.shape != shape for g in gprs)
         ):
-            self._fused = False
             return None
-        from optuna_amd import _hip
-
-        core = _hip.get()
-        if (
-            core is None
-            or not core.available()
-            or self._fixed_samples.shape[0] > core.GP_EHVI_MAX_Q
-        ):
-            self._fused = False
+        core = _fused_core()
+        if core is None or self._fixed_samples.shape[0] > core.GP_EHVI_MAX_Q:
             return None
-        # Our stream must not race torch's producers of these tensors.
-        torch.cuda.synchronize()
-        self._fused_refs = [
-            (
-                g._X_train.contiguous(),
-                g._cov_Y_Y_inv_Y.contiguous(),
-                g._cov_Y_Y_inv.contiguous(),
-                g.inverse_squared_lengthscales.contiguous(),
-            )
-            for g in gprs
-        ]
-        X0 = self._fused_refs[0][0]
-        self._fused = core.GpLogEhviSession(
-            [r[0].data_ptr() for r in self._fused_refs],
-            [r[1].data_ptr() for r in self._fused_refs],
-            [r[2].data_ptr() for r in self._fused_refs],
-            [r[3].data_ptr() for r in self._fused_refs],
+        self._fused_refs = _device_tensors(gprs)
+        return core.GpLogEhviSession(
+            *_pointers(self._fused_refs),
             [float(g.kernel_scale.item()) for g in gprs],
-            int(X0.shape[0]),
-            int(X0.shape[1]),
+            int(shape[0]),
+            int(shape[1]),
             float(self._stabilizing_noise),
             self._fixed_samples.cpu().numpy(),
             self._box_lower.cpu().numpy(),
             self._box_intervals.cpu().numpy(),
         )
-        return self._fused
-
-    def eval_acqf_no_grad(self, x: np.ndarray) -> np.ndarray:
-        session = self._fused_session()
-        if session is not None:
-            x2 = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-            f, _ = session.eval(x2, with_grad=False)
-            return np.asarray(f) if x.ndim > 1 else np.asarray(f)[0]
-        return super().eval_acqf_no_grad(x)
-
-    def eval_acqf_batched_with_grad(self, x: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
-        session = self._fused_session()
-        if session is not None:
-            f, g = session.eval(np.ascontiguousarray(x, dtype=np.float64), with_grad=True)
-            return np.asarray(f), np.asarray(g)
-        return super().eval_acqf_batched_with_grad(x)
-
-    def eval_acqf_with_grad(self, x: np.ndarray) -> tuple[float, np.ndarray]:
-        session = self._fused_session()
-        if session is not None:
-            f, g = session.eval(
-                np.ascontiguousarray(x[None, :], dtype=np.float64), with_grad=True
-            )
-            return float(np.asarray(f)[0]), np.asarray(g)[0]
-        return super().eval_acqf_with_grad(x)
 
 
 class qLogEHVI(BaseAcquisitionFunc):
@@ -819,26 +736,17 @@ class LogCEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
             )
             for c_gpr, c_threshold in zip(constraints_gpr_list, constraints_threshold_list)
         ]
-        self._fused = None
         super().__init__(
             np.mean([gpr.length_scales for gpr in gpr_list], axis=0),
             search_space,
             gpr_list[0].device,
         )
 
-    def _fused_session(self):
-        if self._fused is None:
-            # Y_feasible=None (no feasible trial yet) leaves the feasibility alone.
-            self._fused = (
-                _fused_constrained_session(
-                    self._device,
-                    self._acqf,
-                    self._acqf._gpr_list if self._acqf is not None else [],
-                    self._constraints_acqf_list,
-                )
-                or False
-            )
-        return self._fused or None
+    def _build_fused_session(self):
+        # Y_feasible=None (no feasible trial yet) leaves the feasibility alone.
+        return _fused_constrained_session(
+            self, self._acqf, self._acqf._gpr_list if self._acqf is not None else []
+        )
 
     def eval_acqf(self, x: "torch.Tensor") -> "torch.Tensor":
         feasibility = sum(acqf.eval_acqf(x) for acqf in self._constraints_acqf_list)

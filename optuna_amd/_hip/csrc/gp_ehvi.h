@@ -2,7 +2,7 @@
 // K5 (multi-objective): fused GP log-EHVI forward + gradient over M
 // device-resident GPs, 2 <= M <= 4.
 //
-// Per candidate x and objective m the posterior is the one of gp_logei.h
+// Per candidate x and objective m the posterior is the one of gp_posterior.h
 // (k_gp_cross_cov, a rocBLAS dgemm against the explicit inverse, then
 // mean_m = K_m.alpha_m, var_m = max(scale_m - K_m.V_m, 0) + stab). With the
 // fixed QMC normals eps (Q, M) and the non-dominated boxes lo / iv (J, M):
@@ -38,39 +38,19 @@
 
 #pragma once
 
-#include "gp_logei.h"
+#include "gp_feasibility.h"
 
 constexpr int EHVI_MAX_M = 4;
-constexpr int EHVI_BLOCK = 256;
-constexpr int EHVI_WAVES = EHVI_BLOCK / 64;
 // Boxes per LDS tile: the LDS footprint is fixed whatever J is.
 constexpr int EHVI_BOX_TILE = 128;
 // y and eps are staged whole: (2 * Q * M + 2 * M * tile) doubles of LDS stay
 // under the 64 KiB a launch gets without opting in to more.
 constexpr int EHVI_MAX_Q = 512;
-// A small batch (a local-search step has 10 candidates) spreads the box tiles
-// of each candidate over several workgroups, up to about this many in all.
-constexpr int EHVI_TARGET_BLOCKS = 1024;
-// Ceiling on the (B, N) scratch (K, MP, V per objective) of one evaluation;
-// candidates beyond it are evaluated in chunks.
-constexpr int64_t EHVI_SCRATCH_BUDGET_BYTES = int64_t(256) << 20;
 constexpr double EHVI_EPS = 1e-12;  // the host's _EPS
-
-// Sum of the four per-wavefront partials, in wavefront order, seen by every
-// thread. `red` holds EHVI_WAVES doubles.
-__device__ __forceinline__ double ehvi_block_sum(double v, double* red) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    __syncthreads();  // the previous user of `red` is done
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double out = red[0];
-    for (int w = 1; w < EHVI_WAVES; ++w) out += red[w];
-    return out;
-}
 
 // Posterior of objective m for every candidate of the chunk: the first half
 // of k_gp_logei_final. dsd = d sd / d var, zero where the clamp was active.
-__global__ void __launch_bounds__(EHVI_BLOCK)
+__global__ void __launch_bounds__(GP_BLOCK)
 k_gp_ehvi_posterior(const double* __restrict__ K,      // (B, N)
                     const double* __restrict__ V,      // (B, N) = K @ Cinv
                     const double* __restrict__ alpha,  // (N)
@@ -78,18 +58,18 @@ k_gp_ehvi_posterior(const double* __restrict__ K,      // (B, N)
                     double* __restrict__ mean,    // (B, M)
                     double* __restrict__ sd,      // (B, M)
                     double* __restrict__ dsd) {   // (B, M)
-    __shared__ double red[EHVI_WAVES];
+    __shared__ double red[GP_WAVES];
     const int64_t b = blockIdx.x;
     const double* Kb = K + b * N;
     const double* Vb = V + b * N;
     double acc_m = 0.0, acc_v = 0.0;
-    for (int64_t i = threadIdx.x; i < N; i += EHVI_BLOCK) {
+    for (int64_t i = threadIdx.x; i < N; i += GP_BLOCK) {
         const double k = Kb[i];
         acc_m += k * alpha[i];
         acc_v += k * Vb[i];
     }
-    const double kmean = ehvi_block_sum(acc_m, red);
-    const double kv = ehvi_block_sum(acc_v, red);
+    const double kmean = gp_block_sum(acc_m, red);
+    const double kv = gp_block_sum(acc_v, red);
     if (threadIdx.x == 0) {
         const double raw = scale - kv;
         const bool passes = raw >= 0.0;  // clamp_min passes the gradient here
@@ -107,18 +87,18 @@ constexpr int ehvi_words(int M, bool grad) { return grad ? 1 + 2 * M : 1; }
 // Doubles of dynamic LDS the box kernel needs.
 static size_t ehvi_lds_doubles(int M, int Q, bool grad) {
     return (size_t)Q * M * (grad ? 2 : 1) + 2 * (size_t)M * EHVI_BOX_TILE +
-           (size_t)EHVI_WAVES * ehvi_words(M, grad);
+           (size_t)GP_WAVES * ehvi_words(M, grad);
 }
 
 // Workgroup (b, s) of a (B, S) grid sums the pairs of candidate b with the box
 // tiles s, s + S, ... and writes one partial record. All LDS is one dynamic
 // array:
 //   ys (Q, M) | [eps (Q, M) with GRAD] | lo tile (M, TILE) | iv tile (M, TILE)
-//   | EHVI_WAVES reduction records.
+//   | GP_WAVES reduction records.
 // The tiles are stored objective-major so that consecutive lanes, which hold
 // consecutive boxes, read consecutive doubles.
 template <int M, bool GRAD>
-__global__ void __launch_bounds__(EHVI_BLOCK)
+__global__ void __launch_bounds__(GP_BLOCK)
 k_gp_logehvi(const double* __restrict__ mean,  // (B, M)
              const double* __restrict__ sd,    // (B, M)
              const double* __restrict__ eps,   // (Q, M)
@@ -137,7 +117,7 @@ k_gp_logehvi(const double* __restrict__ mean,  // (B, M)
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
     const int S = gridDim.y;
-    for (int i = tid; i < Q * M; i += EHVI_BLOCK) {
+    for (int i = tid; i < Q * M; i += GP_BLOCK) {
         const int m = i % M;
         const double ev = eps[i];
         ys[i] = mean[b * M + m] + sd[b * M + m] * ev;
@@ -149,7 +129,7 @@ k_gp_logehvi(const double* __restrict__ mean,  // (B, M)
          j0 += (int64_t)S * EHVI_BOX_TILE) {
         const int cnt = (int)min((int64_t)EHVI_BOX_TILE, J - j0);
         __syncthreads();  // the previous tile is consumed (first pass: nothing)
-        for (int i = tid; i < cnt * M; i += EHVI_BLOCK) {
+        for (int i = tid; i < cnt * M; i += GP_BLOCK) {
             const int jj = i / M, m = i % M;
             los[m * EHVI_BOX_TILE + jj] = lo[j0 * M + i];
             ivs[m * EHVI_BOX_TILE + jj] = iv[j0 * M + i];
@@ -159,9 +139,9 @@ k_gp_logehvi(const double* __restrict__ mean,  // (B, M)
         // Pair p = q * cnt + jj, p = tid, tid + 256, ...; (q, jj) advance
         // without a division per pair.
         const int total = Q * cnt;
-        const int dq = EHVI_BLOCK / cnt, dj = EHVI_BLOCK % cnt;
+        const int dq = GP_BLOCK / cnt, dj = GP_BLOCK % cnt;
         int q = tid / cnt, jj = tid % cnt;
-        for (int p = tid; p < total; p += EHVI_BLOCK) {
+        for (int p = tid; p < total; p += GP_BLOCK) {
             double d[M];
             bool open[M];  // neither clamp active
 #pragma unroll
@@ -207,7 +187,7 @@ k_gp_logehvi(const double* __restrict__ mean,  // (B, M)
     __syncthreads();
     if (tid < W) {
         double out = red[tid];
-        for (int w = 1; w < EHVI_WAVES; ++w) out += red[w * W + tid];
+        for (int w = 1; w < GP_WAVES; ++w) out += red[w * W + tid];
         part[(b * S + blockIdx.y) * W + tid] = out;
     }
 }
@@ -215,7 +195,7 @@ k_gp_logehvi(const double* __restrict__ mean,  // (B, M)
 // One thread per candidate: the S partial records in order, then the value
 // and the posterior-side weights.
 template <int M, bool GRAD>
-__global__ void __launch_bounds__(EHVI_BLOCK)
+__global__ void __launch_bounds__(GP_BLOCK)
 k_gp_logehvi_finish(const double* __restrict__ part,  // (B, S, W)
                     const double* __restrict__ dsd,   // (B, M)
                     int S, int Q, int64_t B,
@@ -223,7 +203,7 @@ k_gp_logehvi_finish(const double* __restrict__ part,  // (B, S, W)
                     double* __restrict__ out_wm,    // (B, M), GRAD only
                     double* __restrict__ out_wv) {  // (B, M), GRAD only
     constexpr int W = ehvi_words(M, GRAD);
-    const int64_t b = (int64_t)blockIdx.x * EHVI_BLOCK + threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * GP_BLOCK + threadIdx.x;
     if (b >= B) return;
     double acc[W];
 #pragma unroll
@@ -255,17 +235,17 @@ struct EhviGradArgs {
 // tid % D) owns dimension d over the observations i = g, g + G, ... with
 // G = 256 / D groups, so X is read along its rows and nothing is indexed at
 // run time in registers. The G partials of a dimension are summed in order.
-__global__ void __launch_bounds__(EHVI_BLOCK)
+__global__ void __launch_bounds__(GP_BLOCK)
 k_gp_ehvi_grad(EhviGradArgs P, int M,
                const double* __restrict__ wm,  // (B, M)
                const double* __restrict__ wv,  // (B, M)
                const double* __restrict__ x,   // (B, D)
                int64_t N, int D,
                double* __restrict__ out_grad) {  // (B, D)
-    __shared__ double part[EHVI_BLOCK];
+    __shared__ double part[GP_BLOCK];
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    const int G = EHVI_BLOCK / D;
+    const int G = GP_BLOCK / D;
     const int g = tid / D, d = tid % D;
     double acc = 0.0;
     if (g < G) {
@@ -306,15 +286,9 @@ class GpLogEhviSession {
                      const std::vector<double>& scales, int64_t N, int64_t D,
                      double stab_noise, const arr_f64& eps, const arr_f64& lo,
                      const arr_f64& iv, int64_t scratch_budget_bytes)
-        : M_((int)scales.size()), N_(N), D_(D), stab_(stab_noise),
-          budget_(scratch_budget_bytes) {
-        if (M_ < 2 || M_ > EHVI_MAX_M)
-            throw std::runtime_error("GpLogEhviSession: need 2 <= M <= 4");
-        if ((int)X_ptrs.size() != M_ || (int)alpha_ptrs.size() != M_ ||
-            (int)cinv_ptrs.size() != M_ || (int)eta_ptrs.size() != M_)
-            throw std::runtime_error("GpLogEhviSession: one pointer per objective");
-        if (D < 1 || D > 64) throw std::runtime_error("GpLogEhviSession: need 1 <= D <= 64");
-        if (N < 1) throw std::runtime_error("GpLogEhviSession: N < 1");
+        : N_(N), D_(D), stab_(stab_noise), budget_(scratch_budget_bytes) {
+        M_ = gp_make_refs("GpLogEhviSession", X_ptrs, alpha_ptrs, cinv_ptrs, eta_ptrs,
+                          scales, 2, EHVI_MAX_M, N, D, gp_);
         if (budget_ < 1) throw std::runtime_error("GpLogEhviSession: budget < 1");
         if (eps.ndim() != 2 || lo.ndim() != 2 || iv.ndim() != 2 ||
             eps.shape(1) != M_ || lo.shape(1) != M_ || iv.shape(1) != M_ ||
@@ -327,13 +301,6 @@ class GpLogEhviSession {
                                      std::to_string(EHVI_MAX_Q));
         if (J_ < 1 || J_ > INT32_MAX / EHVI_MAX_M)
             throw std::runtime_error("GpLogEhviSession: box count out of range");
-        for (int m = 0; m < M_; ++m) {
-            X_[m] = reinterpret_cast<const double*>(X_ptrs[m]);
-            alpha_[m] = reinterpret_cast<const double*>(alpha_ptrs[m]);
-            cinv_[m] = reinterpret_cast<const double*>(cinv_ptrs[m]);
-            eta_[m] = reinterpret_cast<const double*>(eta_ptrs[m]);
-            scale_[m] = scales[m];
-        }
         const size_t nq = (size_t)Q_ * M_, nj = (size_t)J_ * M_;
         consts_.reserve(nq + 2 * nj);
         HIP_CHECK(hipMemcpy(consts_.ptr, eps.data(), nq * 8, hipMemcpyHostToDevice));
@@ -342,22 +309,18 @@ class GpLogEhviSession {
                             hipMemcpyHostToDevice));
     }
 
-    // Candidates per chunk: the K / MP / V sets of one chunk fit the budget
-    // (one candidate is the floor). With the gradient every objective keeps
-    // its set; without it one set is reused objective by objective.
+    // Candidates per chunk. With the gradient every objective keeps its
+    // K / MP / V set; without it one set is reused objective by objective.
     int64_t chunk_rows(bool with_grad) const {
-        const int64_t per_row = 3 * N_ * 8 * (with_grad ? M_ : 1);
-        // 65535 is the grid's y extent in k_gp_cross_cov.
-        return std::clamp<int64_t>(budget_ / per_row, 1, 65535);
+        return gp_chunk_rows(budget_, N_, with_grad ? M_ : 1);
     }
     int64_t n_chunks(int64_t B, bool with_grad) const {
-        const int64_t rows = chunk_rows(with_grad);
-        return (B + rows - 1) / rows;
+        return gp_n_chunks(B, chunk_rows(with_grad));
     }
-    // Workgroups per candidate in the box kernel for a chunk of bc candidates.
+    // Workgroups per candidate in the box kernel for a chunk of bc
+    // candidates: at least one tile of boxes each.
     int box_splits(int64_t bc) const {
-        const int64_t tiles = (J_ + EHVI_BOX_TILE - 1) / EHVI_BOX_TILE;
-        return (int)std::clamp<int64_t>((EHVI_TARGET_BLOCKS + bc - 1) / bc, 1, tiles);
+        return gp_splits(bc, (J_ + EHVI_BOX_TILE - 1) / EHVI_BOX_TILE);
     }
 
     // With a constraint set the feasibility term and its gradient are added
@@ -365,27 +328,21 @@ class GpLogEhviSession {
     // objectives are done with it, before the one copy back.
     py::tuple eval(const arr_f64& x, bool with_grad,
                    const GpConstraintSet* constraints = nullptr) {
-        if (x.ndim() != 2 || x.shape(1) != D_)
-            throw std::runtime_error("eval: dim mismatch");
-        if (constraints) feas_check_shape(constraints, N_, D_);
-        const int64_t B = x.shape(0);
-        py::array_t<double> f(B);
-        py::array_t<double> g;
-        if (with_grad) g = py::array_t<double>({B, D_});
-        if (B == 0) return py::make_tuple(f, g);
+        GpEvalIo io(x, D_, with_grad);
+        if (constraints) constraints->check_shape(N_, D_);
+        const int64_t B = io.B;
+        if (B == 0) return io.download(nullptr, nullptr);
 
-        hipStream_t st = g_ws.get_stream();
         const int64_t rows = std::min(chunk_rows(with_grad), B);
         const int n_sets = with_grad ? M_ : 1;
         const int W = ehvi_words(M_, with_grad);
         const size_t nK = (size_t)rows * N_, nBM = (size_t)B * M_,
                      nBD = (size_t)B * D_;
         WsLayout L;
-        // bc * box_splits(bc) < EHVI_TARGET_BLOCKS + bc for every chunk.
         const auto s_x = L.add<double>(nBD), s_mean = L.add<double>(nBM),
                    s_sd = L.add<double>(nBM), s_dsd = L.add<double>(nBM),
                    s_f = L.add<double>(B),
-                   s_part = L.add<double>((size_t)(EHVI_TARGET_BLOCKS + rows) * W),
+                   s_part = L.add<double>(gp_part_records(rows) * W),
                    s_wm = L.add<double>(with_grad ? nBM : 0),
                    s_wv = L.add<double>(with_grad ? nBM : 0),
                    s_g = L.add<double>(with_grad ? nBD : 0),
@@ -393,7 +350,7 @@ class GpLogEhviSession {
                    s_MP = L.add<double>(nK * n_sets),
                    s_V = L.add<double>(nK * n_sets),
                    s_cpart = L.add<double>(
-                       constraints ? feas_part_doubles(constraints, rows, with_grad) : 0);
+                       constraints ? constraints->part_doubles(rows, with_grad) : 0);
         char* base = g_ws.ensure_bytes(L.bytes());
         double *d_x = s_x.in(base), *d_mean = s_mean.in(base),
                *d_sd = s_sd.in(base), *d_dsd = s_dsd.in(base),
@@ -401,8 +358,7 @@ class GpLogEhviSession {
                *d_wm = s_wm.in(base), *d_wv = s_wv.in(base),
                *d_g = s_g.in(base), *d_K = s_K.in(base), *d_MP = s_MP.in(base),
                *d_V = s_V.in(base), *d_cpart = s_cpart.in(base);
-        g_ws.begin_uploads();
-        g_ws.h2d(d_x, x.data(), nBD * 8, st);
+        hipStream_t st = io.upload(d_x);
 
         const size_t lds = ehvi_lds_doubles(M_, (int)Q_, with_grad) * 8;
         rocblas_handle blas = get_blas(st);
@@ -413,23 +369,15 @@ class GpLogEhviSession {
             for (int m = 0; m < M_; ++m) {
                 const size_t set = with_grad ? (size_t)m * nK : 0;
                 double *Km = d_K + set, *MPm = d_MP + set, *Vm = d_V + set;
-                const dim3 grid((unsigned)((N_ + 255) / 256), (unsigned)bc);
-                hipLaunchKernelGGL(k_gp_cross_cov, grid, dim3(256), 0, st, X_[m],
-                                   eta_[m], scale_[m], xc, N_, D_, bc, Km, MPm);
-                // V(bc, N) = K(bc, N) @ Cinv(N, N), as in GpLogEiSession.
-                const double one = 1.0, zero = 0.0;
-                ROCBLAS_CHECK(rocblas_dgemm(
-                    blas, rocblas_operation_none, rocblas_operation_none,
-                    (rocblas_int)N_, (rocblas_int)bc, (rocblas_int)N_, &one,
-                    cinv_[m], (rocblas_int)N_, Km, (rocblas_int)N_, &zero, Vm,
-                    (rocblas_int)N_));
+                const GpRef& gp = gp_[m];
+                gp_enqueue_kv(st, blas, gp, xc, bc, N_, D_, Km, MPm, Vm);
                 hipLaunchKernelGGL(k_gp_ehvi_posterior, dim3((unsigned)bc),
-                                   dim3(EHVI_BLOCK), 0, st, Km, Vm, alpha_[m],
-                                   scale_[m], stab_, N_, m, M_, d_mean + b0 * M_,
+                                   dim3(GP_BLOCK), 0, st, Km, Vm, gp.alpha,
+                                   gp.scale, stab_, N_, m, M_, d_mean + b0 * M_,
                                    d_sd + b0 * M_, d_dsd + b0 * M_);
-                ga.X[m] = X_[m];
-                ga.alpha[m] = alpha_[m];
-                ga.eta[m] = eta_[m];
+                ga.X[m] = gp.X;
+                ga.alpha[m] = gp.alpha;
+                ga.eta[m] = gp.eta;
                 ga.MP[m] = MPm;
                 ga.V[m] = Vm;
             }
@@ -439,22 +387,15 @@ class GpLogEhviSession {
                          with_grad ? d_wv + b0 * M_ : nullptr);
             if (with_grad)
                 hipLaunchKernelGGL(k_gp_ehvi_grad, dim3((unsigned)bc),
-                                   dim3(EHVI_BLOCK), 0, st, ga, M_,
+                                   dim3(GP_BLOCK), 0, st, ga, M_,
                                    d_wm + b0 * M_, d_wv + b0 * M_, xc, N_,
                                    (int)D_, d_g + b0 * D_);
             if (constraints)
-                feas_enqueue_add(constraints, st, blas, xc, bc, with_grad, d_K, d_MP,
-                                 d_V, d_cpart, d_f + b0,
-                                 with_grad ? d_g + b0 * D_ : nullptr);
+                constraints->enqueue(st, blas, xc, bc, with_grad, true, d_K, d_MP, d_V,
+                                     d_cpart, d_f + b0,
+                                     with_grad ? d_g + b0 * D_ : nullptr);
         }
-        HIP_CHECK(hipMemcpyAsync(f.mutable_data(), d_f, B * 8,
-                                 hipMemcpyDeviceToHost, st));
-        if (with_grad)
-            HIP_CHECK(hipMemcpyAsync(g.mutable_data(), d_g, nBD * 8,
-                                     hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipGetLastError());
-        return py::make_tuple(f, g);
+        return io.download(d_f, d_g);
     }
 
   private:
@@ -468,11 +409,11 @@ class GpLogEhviSession {
         const double* iv = lo + (size_t)J_ * M_;
         const int S = box_splits(bc);
         hipLaunchKernelGGL((k_gp_logehvi<M, GRAD>),
-                           dim3((unsigned)bc, (unsigned)S), dim3(EHVI_BLOCK), lds,
+                           dim3((unsigned)bc, (unsigned)S), dim3(GP_BLOCK), lds,
                            st, mean, sd, eps, lo, iv, (int)Q_, (int)J_, part);
         hipLaunchKernelGGL((k_gp_logehvi_finish<M, GRAD>),
-                           dim3((unsigned)((bc + EHVI_BLOCK - 1) / EHVI_BLOCK)),
-                           dim3(EHVI_BLOCK), 0, st, part, dsd, S, (int)Q_, bc, f,
+                           dim3((unsigned)((bc + GP_BLOCK - 1) / GP_BLOCK)),
+                           dim3(GP_BLOCK), 0, st, part, dsd, S, (int)Q_, bc, f,
                            wm, wv);
     }
     template <typename... A>
@@ -487,9 +428,7 @@ class GpLogEhviSession {
         }
     }
 
-    const double *X_[EHVI_MAX_M], *alpha_[EHVI_MAX_M], *cinv_[EHVI_MAX_M],
-        *eta_[EHVI_MAX_M];
-    double scale_[EHVI_MAX_M];
+    GpRef gp_[EHVI_MAX_M];
     int M_;
     int64_t N_, D_, Q_ = 0, J_ = 0;
     double stab_;

@@ -4,7 +4,7 @@
 // and its input gradient over C device-resident constraint GPs,
 // 1 <= C <= FEAS_MAX_C. Every constraint GP has the structure of an objective
 // GP (same X, own eta / alpha / explicit inverse), so the posterior is the one
-// of gp_logei.h: k_gp_cross_cov, a rocBLAS dgemm against the inverse, then
+// of gp_posterior.h: k_gp_cross_cov, a rocBLAS dgemm against the inverse, then
 //   mean = K.alpha,  raw = scale - K.V,  sd = sqrt(max(raw, 0) + stab).
 //
 // CLOSED FORM gradient: with rho = phi(z) / Phi(z),
@@ -29,7 +29,7 @@
 
 #pragma once
 
-#include "gp_ehvi.h"
+#include "gp_posterior.h"
 
 constexpr int FEAS_MAX_C = 16;
 
@@ -64,7 +64,7 @@ static int feas_words(int D, bool grad) { return grad ? 2 + 2 * D : 2; }
 // along its rows and nothing is indexed at run time in registers; the d == 0
 // thread of a group also carries the two posterior sums of its rows.
 template <bool GRAD>
-__global__ void __launch_bounds__(EHVI_BLOCK)
+__global__ void __launch_bounds__(GP_BLOCK)
 k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
                    const double* __restrict__ MP,     // (bc, N)
                    const double* __restrict__ V,      // (bc, N) = K @ Cinv
@@ -73,9 +73,9 @@ k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
                    const double* __restrict__ x,      // (bc, D)
                    int64_t N, int D,
                    double* __restrict__ part) {  // (bc, S, W)
-    __shared__ double red[EHVI_WAVES];
-    __shared__ double part_a[GRAD ? EHVI_BLOCK : 1];
-    __shared__ double part_b[GRAD ? EHVI_BLOCK : 1];
+    __shared__ double red[GP_WAVES];
+    __shared__ double part_a[GRAD ? GP_BLOCK : 1];
+    __shared__ double part_b[GRAD ? GP_BLOCK : 1];
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
     const int S = gridDim.y;
@@ -89,13 +89,13 @@ k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
 
     double acc_m = 0.0, acc_v = 0.0;
     if constexpr (!GRAD) {
-        for (int64_t i = i0 + tid; i < i1; i += EHVI_BLOCK) {
+        for (int64_t i = i0 + tid; i < i1; i += GP_BLOCK) {
             const double k = Kb[i];
             acc_m += k * alpha[i];
             acc_v += k * Vb[i];
         }
     } else {
-        const int G = EHVI_BLOCK / D;
+        const int G = GP_BLOCK / D;
         const int g = tid / D, d = tid % D;
         double acc_a = 0.0, acc_b = 0.0;
         if (g < G) {
@@ -117,15 +117,15 @@ k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
         part_b[tid] = acc_b;
     }
     // The barriers in here also publish part_a / part_b.
-    const double kmean = ehvi_block_sum(acc_m, red);
-    const double kv = ehvi_block_sum(acc_v, red);
+    const double kmean = gp_block_sum(acc_m, red);
+    const double kv = gp_block_sum(acc_v, red);
     if (tid == 0) {
         rec[0] = kmean;
         rec[1] = kv;
     }
     if constexpr (GRAD) {
         if (tid < D) {
-            const int G = EHVI_BLOCK / D;
+            const int G = GP_BLOCK / D;
             double a = part_a[tid], bv = part_b[tid];
             for (int k = 1; k < G; ++k) {
                 a += part_a[k * D + tid];
@@ -142,7 +142,7 @@ k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
 // into out_grad. `accumulate` = 0 writes the outputs (the first user of the
 // buffers), 1 adds to them.
 template <bool GRAD>
-__global__ void __launch_bounds__(EHVI_BLOCK)
+__global__ void __launch_bounds__(GP_BLOCK)
 k_gp_logpi_finish(const double* __restrict__ part,  // (B, S, W)
                   const double* __restrict__ eta,   // (D)
                   double scale, double stab_noise, double threshold, int S,
@@ -150,7 +150,7 @@ k_gp_logpi_finish(const double* __restrict__ part,  // (B, S, W)
                   double* __restrict__ out_f,       // (B)
                   double* __restrict__ out_grad) {  // (B, D), GRAD only
     const int W = GRAD ? 2 + 2 * D : 2;
-    const int64_t t = (int64_t)blockIdx.x * EHVI_BLOCK + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * GP_BLOCK + threadIdx.x;
     const int64_t b = GRAD ? t / D : t;
     const int d = GRAD ? (int)(t % D) : 0;
     if (b >= B) return;
@@ -193,54 +193,37 @@ class GpConstraintSet {
                     const std::vector<double>& scales,
                     const std::vector<double>& thresholds, int64_t N, int64_t D,
                     double stab_noise, int64_t scratch_budget_bytes)
-        : C_((int)scales.size()), N_(N), D_(D), stab_(stab_noise),
-          budget_(scratch_budget_bytes) {
-        if (scales.empty() || scales.size() > (size_t)FEAS_MAX_C)
-            throw std::runtime_error("GpConstraintSet: need 1 <= C <= " +
-                                     std::to_string(FEAS_MAX_C));
-        if ((int)X_ptrs.size() != C_ || (int)alpha_ptrs.size() != C_ ||
-            (int)cinv_ptrs.size() != C_ || (int)eta_ptrs.size() != C_ ||
-            (int)thresholds.size() != C_)
-            throw std::runtime_error(
-                "GpConstraintSet: one pointer, scale and threshold per constraint");
-        if (D < 1 || D > 64) throw std::runtime_error("GpConstraintSet: need 1 <= D <= 64");
-        if (N < 1 || N > INT32_MAX) throw std::runtime_error("GpConstraintSet: N out of range");
+        : N_(N), D_(D), stab_(stab_noise), budget_(scratch_budget_bytes) {
+        C_ = gp_make_refs("GpConstraintSet", X_ptrs, alpha_ptrs, cinv_ptrs, eta_ptrs,
+                          scales, 1, FEAS_MAX_C, N, D, gp_);
+        if ((int)thresholds.size() != C_)
+            throw std::runtime_error("GpConstraintSet: one threshold per constraint");
+        if (N > INT32_MAX) throw std::runtime_error("GpConstraintSet: N out of range");
         if (budget_ < 1) throw std::runtime_error("GpConstraintSet: budget < 1");
-        for (int c = 0; c < C_; ++c) {
-            X_[c] = reinterpret_cast<const double*>(X_ptrs[c]);
-            alpha_[c] = reinterpret_cast<const double*>(alpha_ptrs[c]);
-            cinv_[c] = reinterpret_cast<const double*>(cinv_ptrs[c]);
-            eta_[c] = reinterpret_cast<const double*>(eta_ptrs[c]);
-            scale_[c] = scales[c];
-            thr_[c] = thresholds[c];
-        }
+        std::copy(thresholds.begin(), thresholds.end(), thr_);
     }
 
-    int64_t n_obs() const { return N_; }
-    int64_t dim() const { return D_; }
+    // Throws unless a session over (N, D) can hand its candidates to this set.
+    void check_shape(int64_t N, int64_t D) const {
+        if (N_ != N || D_ != D)
+            throw std::runtime_error("eval: the constraint set was built for another (N, D)");
+    }
 
     // Candidates per chunk of a stand-alone evaluation: one K / MP / V set,
-    // reused constraint by constraint, fits the budget (one candidate is the
-    // floor). The gradient needs no further (rows, N) scratch.
-    int64_t chunk_rows() const {
-        // 65535 is the grid's y extent in k_gp_cross_cov.
-        return std::clamp<int64_t>(budget_ / (3 * N_ * 8), 1, 65535);
-    }
+    // reused constraint by constraint. The gradient needs no further
+    // (rows, N) scratch.
+    int64_t chunk_rows() const { return gp_chunk_rows(budget_, N_, 1); }
     int64_t n_chunks(int64_t B, bool /*with_grad*/) const {
-        const int64_t rows = chunk_rows();
-        return (B + rows - 1) / rows;
+        return gp_n_chunks(B, chunk_rows());
     }
     // Workgroups per candidate in the partial kernel for a chunk of bc
-    // candidates: towards EHVI_TARGET_BLOCKS in all, at least one block's
-    // worth of observations each.
+    // candidates: at least one block's worth of observations each.
     int n_splits(int64_t bc) const {
-        const int64_t slices = (N_ + EHVI_BLOCK - 1) / EHVI_BLOCK;
-        return (int)std::clamp<int64_t>((EHVI_TARGET_BLOCKS + bc - 1) / bc, 1, slices);
+        return gp_splits(bc, (N_ + GP_BLOCK - 1) / GP_BLOCK);
     }
-    // Doubles of partial records for chunks of at most `rows` candidates:
-    // bc * n_splits(bc) < EHVI_TARGET_BLOCKS + bc for every chunk.
+    // Doubles of partial records for chunks of at most `rows` candidates.
     size_t part_doubles(int64_t rows, bool with_grad) const {
-        return (size_t)(EHVI_TARGET_BLOCKS + rows) * feas_words((int)D_, with_grad);
+        return gp_part_records(rows) * feas_words((int)D_, with_grad);
     }
 
     // Enqueue the term for the bc candidates xc: K / MP / V are (bc, N)
@@ -253,47 +236,35 @@ class GpConstraintSet {
         const int S = n_splits(bc);
         const int D = (int)D_;
         for (int c = 0; c < C_; ++c) {
-            const dim3 grid((unsigned)((N_ + 255) / 256), (unsigned)bc);
-            hipLaunchKernelGGL(k_gp_cross_cov, grid, dim3(256), 0, st, X_[c],
-                               eta_[c], scale_[c], xc, N_, D_, bc, K, MP);
-            // V(bc, N) = K(bc, N) @ Cinv(N, N), as in GpLogEiSession.
-            const double one = 1.0, zero = 0.0;
-            ROCBLAS_CHECK(rocblas_dgemm(
-                blas, rocblas_operation_none, rocblas_operation_none,
-                (rocblas_int)N_, (rocblas_int)bc, (rocblas_int)N_, &one, cinv_[c],
-                (rocblas_int)N_, K, (rocblas_int)N_, &zero, V, (rocblas_int)N_));
+            const GpRef& gp = gp_[c];
+            gp_enqueue_kv(st, blas, gp, xc, bc, N_, D_, K, MP, V);
             const int acc = (accumulate || c > 0) ? 1 : 0;
             const dim3 pgrid((unsigned)bc, (unsigned)S);
             if (with_grad) {
-                hipLaunchKernelGGL(k_gp_logpi_partial<true>, pgrid, dim3(EHVI_BLOCK),
-                                   0, st, K, MP, V, alpha_[c], X_[c], xc, N_, D, part);
+                hipLaunchKernelGGL(k_gp_logpi_partial<true>, pgrid, dim3(GP_BLOCK),
+                                   0, st, K, MP, V, gp.alpha, gp.X, xc, N_, D, part);
                 hipLaunchKernelGGL(
                     k_gp_logpi_finish<true>,
-                    dim3((unsigned)((bc * D + EHVI_BLOCK - 1) / EHVI_BLOCK)),
-                    dim3(EHVI_BLOCK), 0, st, part, eta_[c], scale_[c], stab_,
-                    thr_[c], S, D, bc, acc, f, g);
+                    dim3((unsigned)((bc * D + GP_BLOCK - 1) / GP_BLOCK)),
+                    dim3(GP_BLOCK), 0, st, part, gp.eta, gp.scale, stab_, thr_[c], S,
+                    D, bc, acc, f, g);
             } else {
-                hipLaunchKernelGGL(k_gp_logpi_partial<false>, pgrid, dim3(EHVI_BLOCK),
-                                   0, st, K, MP, V, alpha_[c], X_[c], xc, N_, D, part);
+                hipLaunchKernelGGL(k_gp_logpi_partial<false>, pgrid, dim3(GP_BLOCK),
+                                   0, st, K, MP, V, gp.alpha, gp.X, xc, N_, D, part);
                 hipLaunchKernelGGL(
                     k_gp_logpi_finish<false>,
-                    dim3((unsigned)((bc + EHVI_BLOCK - 1) / EHVI_BLOCK)),
-                    dim3(EHVI_BLOCK), 0, st, part, eta_[c], scale_[c], stab_,
-                    thr_[c], S, D, bc, acc, f, g);
+                    dim3((unsigned)((bc + GP_BLOCK - 1) / GP_BLOCK)),
+                    dim3(GP_BLOCK), 0, st, part, gp.eta, gp.scale, stab_, thr_[c], S,
+                    D, bc, acc, f, g);
             }
         }
     }
 
     py::tuple eval(const arr_f64& x, bool with_grad) const {
-        if (x.ndim() != 2 || x.shape(1) != D_)
-            throw std::runtime_error("eval: dim mismatch");
-        const int64_t B = x.shape(0);
-        py::array_t<double> f(B);
-        py::array_t<double> g;
-        if (with_grad) g = py::array_t<double>({B, D_});
-        if (B == 0) return py::make_tuple(f, g);
+        GpEvalIo io(x, D_, with_grad);
+        const int64_t B = io.B;
+        if (B == 0) return io.download(nullptr, nullptr);
 
-        hipStream_t st = g_ws.get_stream();
         const int64_t rows = std::min(chunk_rows(), B);
         const size_t nK = (size_t)rows * N_, nBD = (size_t)B * D_;
         WsLayout L;
@@ -306,44 +277,21 @@ class GpConstraintSet {
         double *d_x = s_x.in(base), *d_f = s_f.in(base), *d_g = s_g.in(base),
                *d_part = s_part.in(base), *d_K = s_K.in(base),
                *d_MP = s_MP.in(base), *d_V = s_V.in(base);
-        g_ws.begin_uploads();
-        g_ws.h2d(d_x, x.data(), nBD * 8, st);
+        hipStream_t st = io.upload(d_x);
         rocblas_handle blas = get_blas(st);
         for (int64_t b0 = 0; b0 < B; b0 += rows) {
             const int64_t bc = std::min(rows, B - b0);
             enqueue(st, blas, d_x + b0 * D_, bc, with_grad, false, d_K, d_MP, d_V,
                     d_part, d_f + b0, with_grad ? d_g + b0 * D_ : nullptr);
         }
-        HIP_CHECK(hipMemcpyAsync(f.mutable_data(), d_f, B * 8,
-                                 hipMemcpyDeviceToHost, st));
-        if (with_grad)
-            HIP_CHECK(hipMemcpyAsync(g.mutable_data(), d_g, nBD * 8,
-                                     hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipGetLastError());
-        return py::make_tuple(f, g);
+        return io.download(d_f, d_g);
     }
 
   private:
-    const double *X_[FEAS_MAX_C], *alpha_[FEAS_MAX_C], *cinv_[FEAS_MAX_C],
-        *eta_[FEAS_MAX_C];
-    double scale_[FEAS_MAX_C], thr_[FEAS_MAX_C];
+    GpRef gp_[FEAS_MAX_C];
+    double thr_[FEAS_MAX_C];
     int C_;
     int64_t N_, D_;
     double stab_;
     int64_t budget_;
 };
-
-static void feas_check_shape(const GpConstraintSet* cs, int64_t N, int64_t D) {
-    if (cs->n_obs() != N || cs->dim() != D)
-        throw std::runtime_error("eval: the constraint set was built for another (N, D)");
-}
-static size_t feas_part_doubles(const GpConstraintSet* cs, int64_t rows, bool with_grad) {
-    return cs->part_doubles(rows, with_grad);
-}
-static void feas_enqueue_add(const GpConstraintSet* cs, hipStream_t st,
-                             rocblas_handle blas, const double* xc, int64_t bc,
-                             bool with_grad, double* K, double* MP, double* V,
-                             double* part, double* f, double* g) {
-    cs->enqueue(st, blas, xc, bc, with_grad, true, K, MP, V, part, f, g);
-}

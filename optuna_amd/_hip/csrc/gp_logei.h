@@ -10,29 +10,12 @@
 // dk_i/dx_d = scale * m52'(r2_i) * 2 eta_d (x_d - X_id) — so
 // grad_d = 2 eta_d (x_d * sum_i c_i - sum_i c_i X_id) with
 // c_i = (w_m alpha_i - 2 w_v V_i) * scale * m52'(r2_i).
-// Tensors stay wherever torch put them: the session takes raw device
-// pointers (same process, same HIP context).
+// The first two steps are gp_posterior.h's.
 // ---------------------------------------------------------------------------
 
 #pragma once
 
-#include <rocblas/rocblas.h>
-
-#include "hip_common.h"
-
-#define ROCBLAS_CHECK(expr)                                                     \
-    do {                                                                        \
-        rocblas_status s_ = (expr);                                             \
-        if (s_ != rocblas_status_success)                                       \
-            throw std::runtime_error("rocBLAS error " + std::to_string(s_));    \
-    } while (0)
-
-static rocblas_handle g_blas = nullptr;
-static rocblas_handle get_blas(hipStream_t st) {
-    if (!g_blas) ROCBLAS_CHECK(rocblas_create_handle(&g_blas));
-    ROCBLAS_CHECK(rocblas_set_stream(g_blas, st));
-    return g_blas;
-}
+#include "gp_feasibility.h"
 
 __device__ __forceinline__ double d_log_ndtr(double z) {
     if (z >= 0.0) return log(0.5 * erfc(-z * 0.7071067811865476));
@@ -50,35 +33,7 @@ __device__ __forceinline__ double d_standard_logei(double z) {
     return (-0.5 * z * z - HALF_LOG_2PI) + log1p(mills);
 }
 
-// Phase 1: cross-covariance K[b, i] = scale * m52(r2) and its radial part.
-__global__ void k_gp_cross_cov(const double* __restrict__ X,  // (N, D)
-                               const double* __restrict__ eta,  // (D)
-                               double scale, const double* __restrict__ x,  // (B, D)
-                               int64_t N, int64_t D, int64_t B,
-                               double* __restrict__ K,    // (B, N)
-                               double* __restrict__ MP) {  // (B, N) scale*m52'(r2)
-    __shared__ double xs[64];
-    __shared__ double et[64];
-    const int64_t b = blockIdx.y;
-    for (int64_t d = threadIdx.x; d < D; d += blockDim.x) {
-        xs[d] = x[b * D + d];
-        et[d] = eta[d];
-    }
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    double r2 = 0.0;
-    for (int64_t d = 0; d < D; ++d) {
-        const double diff = xs[d] - X[i * D + d];
-        r2 += et[d] * diff * diff;
-    }
-    const double u = sqrt(5.0 * r2);
-    const double eu = exp(-u);
-    K[b * N + i] = scale * (eu * ((5.0 / 3.0) * r2 + u + 1.0));
-    MP[b * N + i] = scale * ((-5.0 / 6.0) * (1.0 + u) * eu);
-}
-
-// Phase 3: per-candidate mean/var/log-EI (+ gradient when out_grad != null).
+// Phase 3 (phases 1 and 2 are gp_enqueue_kv): per-candidate mean/var/log-EI (+ gradient when out_grad != null).
 __global__ void k_gp_logei_final(const double* __restrict__ K,      // (B, N)
                                  const double* __restrict__ MP,     // (B, N)
                                  const double* __restrict__ V,      // (B, N) = K @ Cinv
@@ -163,21 +118,6 @@ __global__ void k_gp_logei_final(const double* __restrict__ K,      // (B, N)
     }
 }
 
-// The feasibility term of the constrained acquisitions (gp_feasibility.h),
-// which the sessions add to their own result on the device when handed a
-// constraint set. With no set (nullptr) nothing below does anything.
-class GpConstraintSet;
-// Throws unless the set was built for the same (N, D).
-static void feas_check_shape(const GpConstraintSet* cs, int64_t N, int64_t D);
-// Doubles of partial records for chunks of at most `rows` candidates.
-static size_t feas_part_doubles(const GpConstraintSet* cs, int64_t rows, bool with_grad);
-// Enqueue f += sum_c log Phi(z_c), g += its gradient for the bc candidates xc;
-// K / MP / V are (bc, N) scratch the caller is done with.
-static void feas_enqueue_add(const GpConstraintSet* cs, hipStream_t st,
-                             rocblas_handle blas, const double* xc, int64_t bc,
-                             bool with_grad, double* K, double* MP, double* V,
-                             double* part, double* f, double* g);
-
 // Session over torch-owned device tensors (raw pointers; same HIP context).
 // Built once per fitted GP; evaluations upload only the (B, D) candidates.
 class GpLogEiSession {
@@ -185,11 +125,11 @@ class GpLogEiSession {
     GpLogEiSession(int64_t X_ptr, int64_t alpha_ptr, int64_t cinv_ptr,
                    int64_t eta_ptr, int64_t N, int64_t D, double scale,
                    double stab_noise, double threshold)
-        : X_(reinterpret_cast<const double*>(X_ptr)),
-          alpha_(reinterpret_cast<const double*>(alpha_ptr)),
-          cinv_(reinterpret_cast<const double*>(cinv_ptr)),
-          eta_(reinterpret_cast<const double*>(eta_ptr)),
-          N_(N), D_(D), scale_(scale), stab_(stab_noise), thr_(threshold) {
+        : gp_{reinterpret_cast<const double*>(X_ptr),
+              reinterpret_cast<const double*>(alpha_ptr),
+              reinterpret_cast<const double*>(cinv_ptr),
+              reinterpret_cast<const double*>(eta_ptr), scale},
+          N_(N), D_(D), stab_(stab_noise), thr_(threshold) {
         if (D > 64) throw std::runtime_error("GpLogEiSession: D > 64");
     }
 
@@ -198,67 +138,38 @@ class GpLogEiSession {
     // before the one copy back.
     py::tuple eval(const arr_f64& x, bool with_grad,
                    const GpConstraintSet* constraints = nullptr) {
-        const int64_t B = x.shape(0);
-        if (x.shape(1) != D_) throw std::runtime_error("eval: dim mismatch");
-        if (constraints) {
-            feas_check_shape(constraints, N_, D_);
-            // 65535 is the grid's y extent in k_gp_cross_cov.
-            if (B > 65535) throw std::runtime_error("eval: more than 65535 candidates");
-        }
-        hipStream_t st = g_ws.get_stream();
+        GpEvalIo io(x, D_, with_grad);
+        if (constraints) constraints->check_shape(N_, D_);
+        const int64_t B = io.B;
+        if (B == 0) return io.download(nullptr, nullptr);
+        // The whole batch is one chunk.
+        if (B > GP_GRID_Y_MAX) throw std::runtime_error("eval: more than 65535 candidates");
         const size_t nK = (size_t)B * N_;
         WsLayout L;
         const auto s_K = L.add<double>(nK), s_MP = L.add<double>(nK),
                    s_V = L.add<double>(nK), s_x = L.add<double>((size_t)B * D_),
                    s_f = L.add<double>(B), s_g = L.add<double>((size_t)B * D_),
                    s_part = L.add<double>(
-                       constraints ? feas_part_doubles(constraints, B, with_grad) : 0);
+                       constraints ? constraints->part_doubles(B, with_grad) : 0);
         char* base = g_ws.ensure_bytes(L.bytes());
         double *d_K = s_K.in(base), *d_MP = s_MP.in(base), *d_V = s_V.in(base),
                *d_x = s_x.in(base), *d_f = s_f.in(base), *d_g = s_g.in(base),
                *d_part = s_part.in(base);
-        g_ws.begin_uploads();
-        g_ws.h2d(d_x, x.data(), (size_t)B * D_ * 8, st);
-        {
-            const int block = 256;
-            const dim3 grid((unsigned)((N_ + block - 1) / block), (unsigned)B);
-            hipLaunchKernelGGL(k_gp_cross_cov, grid, dim3(block), 0, st, X_,
-                               eta_, scale_, d_x, N_, D_, B, d_K, d_MP);
-        }
-        {
-            // V(B,N) = K(B,N) @ Cinv(N,N): column-major dgemm with the
-            // symmetric Cinv — C^T = Cinv^T @ K^T == Cinv @ K^T.
-            const double one = 1.0, zero = 0.0;
-            ROCBLAS_CHECK(rocblas_dgemm(get_blas(st), rocblas_operation_none,
-                                        rocblas_operation_none, (rocblas_int)N_,
-                                        (rocblas_int)B, (rocblas_int)N_, &one,
-                                        cinv_, (rocblas_int)N_, d_K,
-                                        (rocblas_int)N_, &zero, d_V,
-                                        (rocblas_int)N_));
-        }
+        hipStream_t st = io.upload(d_x);
+        rocblas_handle blas = get_blas(st);
+        gp_enqueue_kv(st, blas, gp_, d_x, B, N_, D_, d_K, d_MP, d_V);
         hipLaunchKernelGGL(k_gp_logei_final, dim3((unsigned)B), dim3(256), 0,
-                           st, d_K, d_MP, d_V, alpha_, X_, eta_, d_x, scale_,
-                           stab_, thr_, N_, D_, d_f,
+                           st, d_K, d_MP, d_V, gp_.alpha, gp_.X, gp_.eta, d_x,
+                           gp_.scale, stab_, thr_, N_, D_, d_f,
                            with_grad ? d_g : nullptr);
-        if (constraints && B > 0)
-            feas_enqueue_add(constraints, st, get_blas(st), d_x, B, with_grad, d_K,
-                             d_MP, d_V, d_part, d_f, with_grad ? d_g : nullptr);
-        py::array_t<double> f(B);
-        HIP_CHECK(hipMemcpyAsync(f.mutable_data(), d_f, B * 8,
-                                 hipMemcpyDeviceToHost, st));
-        py::array_t<double> g;
-        if (with_grad) {
-            g = py::array_t<double>({B, D_});
-            HIP_CHECK(hipMemcpyAsync(g.mutable_data(), d_g, (size_t)B * D_ * 8,
-                                     hipMemcpyDeviceToHost, st));
-        }
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipGetLastError());
-        return py::make_tuple(f, g);
+        if (constraints)
+            constraints->enqueue(st, blas, d_x, B, with_grad, true, d_K, d_MP, d_V,
+                                 d_part, d_f, with_grad ? d_g : nullptr);
+        return io.download(d_f, d_g);
     }
 
   private:
-    const double *X_, *alpha_, *cinv_, *eta_;
+    GpRef gp_;
     int64_t N_, D_;
-    double scale_, stab_, thr_;
+    double stab_, thr_;
 };

@@ -2,9 +2,12 @@
 // This file holds the includes and the Python bindings only.
 #include "hip_common.h"
 
-#include "gp_ehvi.h"
+// The GP headers in dependency order: the sessions call the constraint set.
+#include "gp_posterior.h"
 #include "gp_feasibility.h"
 #include "gp_logei.h"
+#include "gp_ehvi.h"
+
 #include "mo_host.h"
 #include "mo_rank.h"
 #include "tpe_host.h"
@@ -30,7 +33,7 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("X_ptrs"), py::arg("alpha_ptrs"), py::arg("cinv_ptrs"),
              py::arg("eta_ptrs"), py::arg("scales"), py::arg("thresholds"),
              py::arg("N"), py::arg("D"), py::arg("stab_noise"),
-             py::arg("scratch_budget_bytes") = EHVI_SCRATCH_BUDGET_BYTES)
+             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES)
         .def("n_chunks", &GpConstraintSet::n_chunks, py::arg("B"),
              py::arg("with_grad"))
         .def("n_splits", &GpConstraintSet::n_splits, py::arg("bc"))
@@ -52,14 +55,14 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("X_ptrs"), py::arg("alpha_ptrs"), py::arg("cinv_ptrs"),
              py::arg("eta_ptrs"), py::arg("scales"), py::arg("N"), py::arg("D"),
              py::arg("stab_noise"), py::arg("eps"), py::arg("lo"), py::arg("iv"),
-             py::arg("scratch_budget_bytes") = EHVI_SCRATCH_BUDGET_BYTES)
+             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES)
         .def("n_chunks", &GpLogEhviSession::n_chunks, py::arg("B"),
              py::arg("with_grad"))
         .def("eval", &GpLogEhviSession::eval, py::arg("x"), py::arg("with_grad"),
              py::arg("constraints") = py::none());
     m.attr("GP_EHVI_BOX_TILE") = py::int_(EHVI_BOX_TILE);
     m.attr("GP_EHVI_MAX_Q") = py::int_(EHVI_MAX_Q);
-    m.attr("GP_EHVI_SCRATCH_BUDGET_BYTES") = py::int_(EHVI_SCRATCH_BUDGET_BYTES);
+    m.attr("GP_EHVI_SCRATCH_BUDGET_BYTES") = py::int_(GP_SCRATCH_BUDGET_BYTES);
     py::class_<Hssp3dSession>(m, "Hssp3dSession")
         .def(py::init<const arr_f64&, double, double, double>(), py::arg("cand"),
              py::arg("ref_x"), py::arg("ref_y"), py::arg("ref_z"))
