@@ -201,13 +201,21 @@ def _fused_core():
 
 def _device_ready(gpr: GPRegressor) -> bool:
     """Whether a native session can take ``gpr`` as raw pointers: an explicit
-    inverse, no running rows, no categorical dimension and D <= 64."""
+    inverse, no running rows and D <= 64 (categorical columns go along as
+    ``_cat_mask``)."""
     return (
         gpr._cov_Y_Y_inv is not None
         and gpr._X_all is gpr._X_train
-        and not bool(gpr._is_categorical.any())
         and gpr._X_train.shape[1] <= 64
     )
+
+
+def _cat_mask(is_categorical: "torch.Tensor | np.ndarray") -> int:
+    """The categorical columns as the sessions' ``cat_mask``: bit d = column d."""
+    flags = np.asarray(
+        is_categorical.cpu() if isinstance(is_categorical, torch.Tensor) else is_categorical
+    )
+    return sum(1 << int(d) for d in np.flatnonzero(flags))
 
 
 def _device_tensors(gprs: list[GPRegressor]) -> "list[list[torch.Tensor]]":
@@ -312,6 +320,7 @@ class LogEI(_FusedEntryPoints, BaseAcquisitionFunc):
             float(gpr.kernel_scale.item()),
             float(self._stabilizing_noise),
             float(self._threshold),
+            cat_mask=_cat_mask(gpr._is_categorical),
         )
 
 
@@ -480,6 +489,7 @@ def _fused_constrained_session(
         int(shape[0]),
         int(shape[1]),
         float(constraints_acqf_list[0]._stabilizing_noise),
+        cat_mask=_cat_mask(c_gprs[0]._is_categorical),
     )
     return _FusedConstrained(objective, constraints)
 
@@ -639,6 +649,7 @@ class LogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
             self._fixed_samples.cpu().numpy(),
             self._box_lower.cpu().numpy(),
             self._box_intervals.cpu().numpy(),
+            cat_mask=_cat_mask(gprs[0]._is_categorical),
         )
 
 

@@ -120,6 +120,49 @@ def _ard_sqdist_gemm(
     return sq.clamp_min_(0.0)
 
 
+def _categorical_columns(is_categorical: "torch.Tensor | np.ndarray") -> list[int]:
+    """The categorical column numbers as host ints."""
+    if isinstance(is_categorical, np.ndarray):
+        return np.flatnonzero(is_categorical).tolist()
+    return torch.nonzero(is_categorical).flatten().tolist()
+
+
+def _mixed_sqdist(
+    X1: "torch.Tensor",
+    X2: "torch.Tensor",
+    eta: "torch.Tensor",
+    is_categorical: "torch.Tensor | np.ndarray",
+) -> "torch.Tensor":
+    """ARD-weighted distance of a mixed space: no (B, N, D) materialization.
+
+    The continuous columns go through ``_ard_sqdist_gemm``; every categorical
+    column d adds the Hamming term eta_d * [x_d != y_d], one (B, N) term at a
+    time. Differentiable in ``X1`` on the continuous columns; the comparison
+    has no gradient, so it is zero on the categorical ones. ``is_categorical``
+    given as a host array spares a device regressor the synchronisation.
+    """
+    cat = _categorical_columns(is_categorical)
+    if not cat:
+        return _ard_sqdist_gemm(X1, X2, eta)
+    n_dims = X1.shape[-1]
+    if len(cat) == n_dims:
+        sqdist = torch.zeros(
+            X1.shape[:-1] + X2.shape[-2:-1], dtype=X1.dtype, device=X1.device
+        )
+    else:
+        cat_set = set(cat)
+        cont = torch.tensor(
+            [d for d in range(n_dims) if d not in cat_set], device=X1.device
+        )
+        sqdist = _ard_sqdist_gemm(
+            X1.index_select(-1, cont), X2.index_select(-1, cont), eta.index_select(0, cont)
+        )
+    for d in cat:
+        differs = X1[..., :, None, d] != X2[..., None, :, d]
+        sqdist = sqdist + eta[d] * differs
+    return sqdist
+
+
 class GPRegressor:
     # Build the (N, N, D) per-dim squared-difference tensor only up to this many
     # observations; above it every training-covariance evaluation goes through
@@ -144,9 +187,10 @@ class GPRegressor:
         self._squared_X_diff: "torch.Tensor | None" = None
         n_obs = X_train.shape[0]
         going_to_device = n_obs >= self._DEVICE_FIT_MIN_OBS and torch.cuda.is_available()
-        if is_categorical.any() or (
-            n_obs <= self._MAX_DENSE_SQDIFF_OBS and not going_to_device
-        ):
+        # The categorical columns on the host: kernel() needs them per call and
+        # must not synchronise a device regressor to learn them.
+        self._is_categorical_host = is_categorical.detach().cpu().numpy().astype(bool)
+        if n_obs <= self._MAX_DENSE_SQDIFF_OBS and not going_to_device:
             sqd = (X_train.unsqueeze(-2) - X_train.unsqueeze(-3)).square_()
             if is_categorical.any():
                 # Hamming distance on categorical axes.
@@ -199,6 +243,14 @@ class GPRegressor:
             self._y_all = self._y_train
         return self
 
+    def _cat_host(self) -> np.ndarray:
+        """``_is_categorical`` as a host bool array (cached: no device sync per call)."""
+        host = self.__dict__.get("_is_categorical_host")
+        if host is None:
+            host = self._is_categorical.detach().cpu().numpy().astype(bool)
+            self._is_categorical_host = host
+        return host
+
     def kernel(
         self, X1: "torch.Tensor | None" = None, X2: "torch.Tensor | None" = None
     ) -> "torch.Tensor":
@@ -206,16 +258,17 @@ class GPRegressor:
         if X1 is None:
             assert X2 is None
             if self._squared_X_diff is None:
-                # Large no-categorical history: GEMM identity, O(N^2 D) flops
-                # through MFMA instead of an (N, N, D) broadcast tensor.
-                sqdist = _ard_sqdist_gemm(self._X_train, self._X_train, eta)
+                # Large history: GEMM identity (plus one Hamming term per
+                # categorical column), O(N^2 D) flops through MFMA instead of
+                # an (N, N, D) broadcast tensor.
+                sqdist = _mixed_sqdist(self._X_train, self._X_train, eta, self._cat_host())
                 return matern52_of_sqdist(sqdist) * self.kernel_scale
             sqd = self._squared_X_diff
         else:
             if X2 is None:
                 X2 = self._X_train
-            if not self._is_categorical.any() and X1.ndim >= 2:
-                sqdist = _ard_sqdist_gemm(X1, X2, eta)
+            if X1.ndim >= 2:
+                sqdist = _mixed_sqdist(X1, X2, eta, self._cat_host())
                 return matern52_of_sqdist(sqdist) * self.kernel_scale
             sqd = (X1 - X2 if X1.ndim == 1 else X1.unsqueeze(-2) - X2.unsqueeze(-3)).square_()
             if self._is_categorical.any():
@@ -463,7 +516,9 @@ class GPRegressor:
         lengthscale gradient uses
           d/d eta_d = sum_ij W_ij (x_id - x_jd)^2
                     = ((r + c) · X_d²) − 2 X_dᵀ (W X_d)
-        with r/c the row/col sums of W — three GEMM-class ops total. Only the
+        with r/c the row/col sums of W — three GEMM-class ops total; a
+        categorical column takes sum_ij W_ij [x_id != x_jd] over its own (N, N)
+        mask instead, and r2 comes from ``_mixed_sqdist``. Only the
         raw-parameter vector and the scalar loss/gradient cross the PCIe bus
         per L-BFGS iteration when X lives on the device.
         """
@@ -479,7 +534,8 @@ class GPRegressor:
                 if deterministic_objective
                 else noise_raw + minimum_noise
             )
-            r2 = _ard_sqdist_gemm(X, X, eta)
+            is_cat = self._cat_host()
+            r2 = _mixed_sqdist(X, X, eta, is_cat)
             u = torch.sqrt(5.0 * r2)
             eu = torch.exp(-u)
             M = eu * ((5.0 / 3.0) * r2 + u + 1.0)
@@ -502,6 +558,9 @@ class GPRegressor:
             W = (0.5 * scale) * (A * Mp)
             rc = W.sum(1) + W.sum(0)
             g_eta = X.square().T.mv(rc) - 2.0 * (X * W.matmul(X)).sum(0)
+            for d in _categorical_columns(is_cat):
+                # Hamming column: d/d eta_d = sum_ij W_ij [x_id != x_jd].
+                g_eta[d] = (W * (X[:, None, d] != X[None, :, d])).sum()
             g_scale = 0.5 * (A * M).sum()
             g_noise = 0.5 * A.diagonal().sum()
             gp_eta = 0.1 / (eta * eta) - 0.1
@@ -546,7 +605,6 @@ class GPRegressor:
         use_device = (
             self._X_train.shape[0] >= self._DEVICE_FIT_MIN_OBS
             and torch.cuda.is_available()
-            and not self._is_categorical.any()
         )
         if log_prior is default_log_prior and (use_device or self._squared_X_diff is None):
             # Closed-form GEMM-structured loss/grad. On the MI355X the whole

@@ -2,7 +2,9 @@
 
 QMC presample → roulette-wheel warm starts → batched local search alternating
 lengthscale-preconditioned L-BFGS-B on the continuous dims with per-dim discrete
-moves (exhaustive ≤16 choices, interpolated Brent line search otherwise).
+moves (exhaustive ≤16 choices, interpolated Brent line search otherwise). Where
+the acquisition runs through a native session, the exhaustive move of all chains
+is one batched evaluation.
 
 Parity: reference ``optuna/_gp/optim_mixed.py`` (_gradient_ascent_batched :29,
 discrete search :97-205, local_search_mixed_batched :232, optimize_acqf_mixed
@@ -140,7 +142,52 @@ def _discrete_line_search(
     return initial_params, initial_fval, False
 
 
+def _exhaustive_search_batched(
+    acqf: "BaseAcquisitionFunc",
+    params_batched: np.ndarray,
+    fvals: np.ndarray,
+    param_idx: int,
+    choices: np.ndarray,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``_exhaustive_search`` of every chain in one ``eval_acqf_no_grad`` call.
+
+    The candidates of all chains are stacked into one batch; each chain then
+    decides as ``_exhaustive_search`` does: its first maximum, taken only when
+    strictly greater than the chain's current value. The split count of the
+    fused kernels depends on the batch size, so a chain's values can differ in
+    the last bits from a per-chain call; the choice can differ only on such
+    ties.
+    """
+    n_chains = len(params_batched)
+    updated = np.zeros(n_chains, dtype=bool)
+    if len(choices) == 1 or n_chains == 0:
+        return params_batched, fvals, updated
+    others = [choices[choices != x[param_idx]] for x in params_batched]
+    counts = np.array([len(o) for o in others])
+    candidates = np.repeat(params_batched, counts, axis=0)
+    candidates[:, param_idx] = np.concatenate(others)
+    cand_fvals = acqf.eval_acqf_no_grad(candidates)
+    out_xs, out_fvals = params_batched.copy(), fvals.copy()
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    for b in range(n_chains):
+        chain = cand_fvals[starts[b] : starts[b + 1]]
+        best = int(np.argmax(chain))
+        if chain[best] > fvals[b]:
+            out_xs[b] = candidates[starts[b] + best]
+            out_fvals[b] = float(chain[best])
+            updated[b] = True
+    return out_xs, out_fvals, updated
+
+
 _MAX_EXHAUSTIVE_CHOICES = 16
+
+
+def _takes_exhaustive_route(
+    acqf: "BaseAcquisitionFunc", param_idx: int, choices: np.ndarray
+) -> bool:
+    return bool(
+        acqf.search_space.is_categorical[param_idx] or len(choices) <= _MAX_EXHAUSTIVE_CHOICES
+    )
 
 
 def _local_search_discrete(
@@ -151,9 +198,16 @@ def _local_search_discrete(
     choices: np.ndarray,
     xtol: float,
 ) -> tuple[np.ndarray, float, bool]:
-    if acqf.search_space.is_categorical[param_idx] or len(choices) <= _MAX_EXHAUSTIVE_CHOICES:
+    if _takes_exhaustive_route(acqf, param_idx, choices):
         return _exhaustive_search(acqf, initial_params, initial_fval, param_idx, choices)
     return _discrete_line_search(acqf, initial_params, initial_fval, param_idx, choices, xtol)
+
+
+def _has_fused_session(acqf: "BaseAcquisitionFunc") -> bool:
+    """Whether ``acqf`` evaluates through a native session, where one call for
+    all chains costs about what one call for one chain does."""
+    fused_session = getattr(acqf, "_fused_session", None)
+    return fused_session is not None and fused_session() is not None
 
 
 def local_search_mixed_batched(
@@ -166,6 +220,10 @@ def local_search_mixed_batched(
     discrete_xtols = [
         np.min(np.diff(choices), initial=np.inf) / 4 for choices in discrete_choices
     ]
+
+    # With a native session the exhaustive step of all chains is one call; the
+    # torch and CPU paths keep their per-chain calls.
+    batch_exhaustive = _has_fused_session(acqf)
 
     best_xs = xs0.copy()
     best_fvals = acqf.eval_acqf_no_grad(best_xs)
@@ -185,11 +243,18 @@ def local_search_mixed_batched(
             remaining = remaining[~converged]
             if remaining.size == 0:
                 return best_xs, best_fvals
-            updated = np.zeros(len(remaining), dtype=bool)
-            for b, row in enumerate(remaining):
-                best_xs[row], best_fvals[row], updated[b] = _local_search_discrete(
-                    acqf, best_xs[row], best_fvals[row], i, choices, xtol
+            if batch_exhaustive and _takes_exhaustive_route(acqf, i, choices):
+                best_xs[remaining], best_fvals[remaining], updated = (
+                    _exhaustive_search_batched(
+                        acqf, best_xs[remaining], best_fvals[remaining], i, choices
+                    )
                 )
+            else:
+                updated = np.zeros(len(remaining), dtype=bool)
+                for b, row in enumerate(remaining):
+                    best_xs[row], best_fvals[row], updated[b] = _local_search_discrete(
+                        acqf, best_xs[row], best_fvals[row], i, choices, xtol
+                    )
             last_changed = np.where(updated, i, last_changed)
 
         converged = last_changed == CONTINUOUS

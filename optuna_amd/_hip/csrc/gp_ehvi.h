@@ -29,7 +29,8 @@
 //   wv_m = sum_q eps[q,m] df/dy[q,m] / (2 sd_m)   (0 where var_m was clamped)
 // and the input gradient is the LogEI one summed over the objectives:
 //   grad_d = sum_m 2 eta_md (x_d sum_i c_mi - sum_i c_mi X_id),
-//   c_mi = (wm_m alpha_mi - 2 wv_m V_mi) * MP_mi.
+//   c_mi = (wm_m alpha_mi - 2 wv_m V_mi) * MP_mi,
+// and exactly 0 on a categorical column (gp_posterior.h's cat_mask).
 // All reductions run in a fixed order (wavefront shuffles, the four wavefronts
 // through LDS, then the workgroups of a candidate in index order) and there
 // are no floating-point atomics, so equal inputs in equal batches give equal
@@ -240,7 +241,7 @@ k_gp_ehvi_grad(EhviGradArgs P, int M,
                const double* __restrict__ wm,  // (B, M)
                const double* __restrict__ wv,  // (B, M)
                const double* __restrict__ x,   // (B, D)
-               int64_t N, int D,
+               int64_t N, int D, uint64_t cat_mask,
                double* __restrict__ out_grad) {  // (B, D)
     __shared__ double part[GP_BLOCK];
     const int tid = threadIdx.x;
@@ -248,7 +249,8 @@ k_gp_ehvi_grad(EhviGradArgs P, int M,
     const int G = GP_BLOCK / D;
     const int g = tid / D, d = tid % D;
     double acc = 0.0;
-    if (g < G) {
+    // A categorical column keeps acc = 0: its Hamming term does not move with x.
+    if (g < G && !gp_is_cat(cat_mask, d)) {
         const double xd = x[b * D + d];
         for (int m = 0; m < M; ++m) {
             const double w_m = wm[b * M + m], w_v = wv[b * M + m];
@@ -285,10 +287,11 @@ class GpLogEhviSession {
                      const std::vector<int64_t>& eta_ptrs,
                      const std::vector<double>& scales, int64_t N, int64_t D,
                      double stab_noise, const arr_f64& eps, const arr_f64& lo,
-                     const arr_f64& iv, int64_t scratch_budget_bytes)
+                     const arr_f64& iv, int64_t scratch_budget_bytes,
+                     uint64_t cat_mask = 0)
         : N_(N), D_(D), stab_(stab_noise), budget_(scratch_budget_bytes) {
         M_ = gp_make_refs("GpLogEhviSession", X_ptrs, alpha_ptrs, cinv_ptrs, eta_ptrs,
-                          scales, 2, EHVI_MAX_M, N, D, gp_);
+                          scales, 2, EHVI_MAX_M, N, D, cat_mask, gp_);
         if (budget_ < 1) throw std::runtime_error("GpLogEhviSession: budget < 1");
         if (eps.ndim() != 2 || lo.ndim() != 2 || iv.ndim() != 2 ||
             eps.shape(1) != M_ || lo.shape(1) != M_ || iv.shape(1) != M_ ||
@@ -329,7 +332,7 @@ class GpLogEhviSession {
     py::tuple eval(const arr_f64& x, bool with_grad,
                    const GpConstraintSet* constraints = nullptr) {
         GpEvalIo io(x, D_, with_grad);
-        if (constraints) constraints->check_shape(N_, D_);
+        if (constraints) constraints->check_shape(N_, D_, gp_[0].cat_mask);
         const int64_t B = io.B;
         if (B == 0) return io.download(nullptr, nullptr);
 
@@ -389,7 +392,7 @@ class GpLogEhviSession {
                 hipLaunchKernelGGL(k_gp_ehvi_grad, dim3((unsigned)bc),
                                    dim3(GP_BLOCK), 0, st, ga, M_,
                                    d_wm + b0 * M_, d_wv + b0 * M_, xc, N_,
-                                   (int)D_, d_g + b0 * D_);
+                                   (int)D_, gp_[0].cat_mask, d_g + b0 * D_);
             if (constraints)
                 constraints->enqueue(st, blas, xc, bc, with_grad, true, d_K, d_MP, d_V,
                                      d_cpart, d_f + b0,

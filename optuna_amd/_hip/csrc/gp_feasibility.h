@@ -19,7 +19,9 @@
 // yields the posterior sums and the gradient sums together, and that pass can
 // be split over S workgroups per candidate (a local-search step has about 10
 // candidates). A finish kernel adds the S records in order and adds the result
-// to whatever the objective term left in out_f / out_grad.
+// to whatever the objective term left in out_f / out_grad. On a categorical
+// column (gp_posterior.h's cat_mask) the distance term does not move with x:
+// A_d = Bv_d = 0, the walk skips it and the finish writes, or adds, exactly 0.
 //
 // All reductions run in a fixed order (wavefront shuffles, the wavefronts
 // through LDS, the row groups of a dimension in order, the workgroups of a
@@ -71,7 +73,7 @@ k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
                    const double* __restrict__ alpha,  // (N)
                    const double* __restrict__ X,      // (N, D)
                    const double* __restrict__ x,      // (bc, D)
-                   int64_t N, int D,
+                   int64_t N, int D, uint64_t cat_mask,
                    double* __restrict__ part) {  // (bc, S, W)
     __shared__ double red[GP_WAVES];
     __shared__ double part_a[GRAD ? GP_BLOCK : 1];
@@ -98,12 +100,15 @@ k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
         const int G = GP_BLOCK / D;
         const int g = tid / D, d = tid % D;
         double acc_a = 0.0, acc_b = 0.0;
-        if (g < G) {
+        // A categorical column has A_d = Bv_d = 0: its threads sit the walk
+        // out, but for the d == 0 one, which carries the posterior sums.
+        const bool cat = gp_is_cat(cat_mask, d);
+        if (g < G && (!cat || d == 0)) {
             const double* MPb = MP + b * N;
             const double xd = x[b * D + d];
             for (int64_t i = i0 + g; i < i1; i += G) {
                 const double al = alpha[i], v = Vb[i];
-                const double w = MPb[i] * (xd - X[i * D + d]);
+                const double w = cat ? 0.0 : MPb[i] * (xd - X[i * D + d]);
                 acc_a += al * w;
                 acc_b += v * w;
                 if (d == 0) {
@@ -146,7 +151,7 @@ __global__ void __launch_bounds__(GP_BLOCK)
 k_gp_logpi_finish(const double* __restrict__ part,  // (B, S, W)
                   const double* __restrict__ eta,   // (D)
                   double scale, double stab_noise, double threshold, int S,
-                  int D, int64_t B, int accumulate,
+                  int D, int64_t B, int accumulate, uint64_t cat_mask,
                   double* __restrict__ out_f,       // (B)
                   double* __restrict__ out_grad) {  // (B, D), GRAD only
     const int W = GRAD ? 2 + 2 * D : 2;
@@ -175,7 +180,9 @@ k_gp_logpi_finish(const double* __restrict__ part,  // (B, S, W)
         }
         const double w_m = rho / sd;
         const double w_v = passes ? -rho * z / (2.0 * sd * sd) : 0.0;
-        const double gd = 2.0 * eta[d] * (w_m * a - 2.0 * w_v * bv);
+        const double gd = gp_is_cat(cat_mask, d)
+                              ? 0.0
+                              : 2.0 * eta[d] * (w_m * a - 2.0 * w_v * bv);
         out_grad[b * D + d] = accumulate ? out_grad[b * D + d] + gd : gd;
     }
 }
@@ -192,10 +199,12 @@ class GpConstraintSet {
                     const std::vector<int64_t>& eta_ptrs,
                     const std::vector<double>& scales,
                     const std::vector<double>& thresholds, int64_t N, int64_t D,
-                    double stab_noise, int64_t scratch_budget_bytes)
-        : N_(N), D_(D), stab_(stab_noise), budget_(scratch_budget_bytes) {
+                    double stab_noise, int64_t scratch_budget_bytes,
+                    uint64_t cat_mask = 0)
+        : N_(N), D_(D), stab_(stab_noise), budget_(scratch_budget_bytes),
+          cat_mask_(cat_mask) {
         C_ = gp_make_refs("GpConstraintSet", X_ptrs, alpha_ptrs, cinv_ptrs, eta_ptrs,
-                          scales, 1, FEAS_MAX_C, N, D, gp_);
+                          scales, 1, FEAS_MAX_C, N, D, cat_mask, gp_);
         if ((int)thresholds.size() != C_)
             throw std::runtime_error("GpConstraintSet: one threshold per constraint");
         if (N > INT32_MAX) throw std::runtime_error("GpConstraintSet: N out of range");
@@ -203,10 +212,14 @@ class GpConstraintSet {
         std::copy(thresholds.begin(), thresholds.end(), thr_);
     }
 
-    // Throws unless a session over (N, D) can hand its candidates to this set.
-    void check_shape(int64_t N, int64_t D) const {
+    // Throws unless a session over (N, D) and the categorical columns
+    // `cat_mask` can hand its candidates to this set: another mask is another
+    // search space.
+    void check_shape(int64_t N, int64_t D, uint64_t cat_mask) const {
         if (N_ != N || D_ != D)
             throw std::runtime_error("eval: the constraint set was built for another (N, D)");
+        if (cat_mask_ != cat_mask)
+            throw std::runtime_error("eval: the constraint set was built for another cat_mask");
     }
 
     // Candidates per chunk of a stand-alone evaluation: one K / MP / V set,
@@ -242,20 +255,22 @@ class GpConstraintSet {
             const dim3 pgrid((unsigned)bc, (unsigned)S);
             if (with_grad) {
                 hipLaunchKernelGGL(k_gp_logpi_partial<true>, pgrid, dim3(GP_BLOCK),
-                                   0, st, K, MP, V, gp.alpha, gp.X, xc, N_, D, part);
+                                   0, st, K, MP, V, gp.alpha, gp.X, xc, N_, D, cat_mask_,
+                                   part);
                 hipLaunchKernelGGL(
                     k_gp_logpi_finish<true>,
                     dim3((unsigned)((bc * D + GP_BLOCK - 1) / GP_BLOCK)),
                     dim3(GP_BLOCK), 0, st, part, gp.eta, gp.scale, stab_, thr_[c], S,
-                    D, bc, acc, f, g);
+                    D, bc, acc, cat_mask_, f, g);
             } else {
                 hipLaunchKernelGGL(k_gp_logpi_partial<false>, pgrid, dim3(GP_BLOCK),
-                                   0, st, K, MP, V, gp.alpha, gp.X, xc, N_, D, part);
+                                   0, st, K, MP, V, gp.alpha, gp.X, xc, N_, D, cat_mask_,
+                                   part);
                 hipLaunchKernelGGL(
                     k_gp_logpi_finish<false>,
                     dim3((unsigned)((bc + GP_BLOCK - 1) / GP_BLOCK)),
                     dim3(GP_BLOCK), 0, st, part, gp.eta, gp.scale, stab_, thr_[c], S,
-                    D, bc, acc, f, g);
+                    D, bc, acc, cat_mask_, f, g);
             }
         }
     }
@@ -294,4 +309,5 @@ class GpConstraintSet {
     int64_t N_, D_;
     double stab_;
     int64_t budget_;
+    uint64_t cat_mask_;
 };

@@ -9,7 +9,9 @@
 // df/dvar = exp(logphi(z) - logg(z))/(2 var),
 // dk_i/dx_d = scale * m52'(r2_i) * 2 eta_d (x_d - X_id) — so
 // grad_d = 2 eta_d (x_d * sum_i c_i - sum_i c_i X_id) with
-// c_i = (w_m alpha_i - 2 w_v V_i) * scale * m52'(r2_i).
+// c_i = (w_m alpha_i - 2 w_v V_i) * scale * m52'(r2_i). On a categorical
+// column (a bit of cat_mask) r2 holds the Hamming indicator, which does not
+// move with x: grad_d is exactly 0 there.
 // The first two steps are gp_posterior.h's.
 // ---------------------------------------------------------------------------
 
@@ -43,6 +45,7 @@ __global__ void k_gp_logei_final(const double* __restrict__ K,      // (B, N)
                                  const double* __restrict__ x,      // (B, D)
                                  double scale, double stab_noise,
                                  double threshold, int64_t N, int64_t D,
+                                 uint64_t cat_mask,
                                  double* __restrict__ out_f,     // (B)
                                  double* __restrict__ out_grad) {  // (B, D) or null
     constexpr int MAXD = 64;
@@ -104,6 +107,7 @@ __global__ void k_gp_logei_final(const double* __restrict__ K,      // (B, N)
     }
     const double sum_c = red_a[0];
     for (int64_t d = 0; d < D; ++d) {
+        if (gp_is_cat(cat_mask, (int)d)) continue;  // block-uniform; red_d[d] unused
         red_b[threadIdx.x] = accd[d];
         __syncthreads();
         for (int stride = blockDim.x / 2; stride > 0; stride >>= 1) {
@@ -113,8 +117,12 @@ __global__ void k_gp_logei_final(const double* __restrict__ K,      // (B, N)
         if (threadIdx.x == 0) red_d[d] = red_b[0];
         __syncthreads();
     }
+    // The Hamming term of a categorical column does not move with x.
     for (int64_t d = threadIdx.x; d < D; d += blockDim.x) {
-        out_grad[b * D + d] = 2.0 * eta[d] * (x[b * D + d] * sum_c - red_d[d]);
+        out_grad[b * D + d] =
+            gp_is_cat(cat_mask, (int)d)
+                ? 0.0
+                : 2.0 * eta[d] * (x[b * D + d] * sum_c - red_d[d]);
     }
 }
 
@@ -124,13 +132,10 @@ class GpLogEiSession {
   public:
     GpLogEiSession(int64_t X_ptr, int64_t alpha_ptr, int64_t cinv_ptr,
                    int64_t eta_ptr, int64_t N, int64_t D, double scale,
-                   double stab_noise, double threshold)
-        : gp_{reinterpret_cast<const double*>(X_ptr),
-              reinterpret_cast<const double*>(alpha_ptr),
-              reinterpret_cast<const double*>(cinv_ptr),
-              reinterpret_cast<const double*>(eta_ptr), scale},
-          N_(N), D_(D), stab_(stab_noise), thr_(threshold) {
-        if (D > 64) throw std::runtime_error("GpLogEiSession: D > 64");
+                   double stab_noise, double threshold, uint64_t cat_mask = 0)
+        : N_(N), D_(D), stab_(stab_noise), thr_(threshold) {
+        gp_make_refs("GpLogEiSession", {X_ptr}, {alpha_ptr}, {cinv_ptr}, {eta_ptr},
+                     {scale}, 1, 1, N, D, cat_mask, &gp_);
     }
 
     // With a constraint set the feasibility term and its gradient are added
@@ -139,7 +144,7 @@ class GpLogEiSession {
     py::tuple eval(const arr_f64& x, bool with_grad,
                    const GpConstraintSet* constraints = nullptr) {
         GpEvalIo io(x, D_, with_grad);
-        if (constraints) constraints->check_shape(N_, D_);
+        if (constraints) constraints->check_shape(N_, D_, gp_.cat_mask);
         const int64_t B = io.B;
         if (B == 0) return io.download(nullptr, nullptr);
         // The whole batch is one chunk.
@@ -160,7 +165,7 @@ class GpLogEiSession {
         gp_enqueue_kv(st, blas, gp_, d_x, B, N_, D_, d_K, d_MP, d_V);
         hipLaunchKernelGGL(k_gp_logei_final, dim3((unsigned)B), dim3(256), 0,
                            st, d_K, d_MP, d_V, gp_.alpha, gp_.X, gp_.eta, d_x,
-                           gp_.scale, stab_, thr_, N_, D_, d_f,
+                           gp_.scale, stab_, thr_, N_, D_, gp_.cat_mask, d_f,
                            with_grad ? d_g : nullptr);
         if (constraints)
             constraints->enqueue(st, blas, d_x, B, with_grad, true, d_K, d_MP, d_V,

@@ -45,13 +45,18 @@ __device__ __forceinline__ double gp_block_sum(double v, double* red) {
     return out;
 }
 
-// Cross-covariance K[b, i] = scale * m52(r2) and its radial part.
+// Cross-covariance K[b, i] = scale * m52(r2) and its radial part. MIXED adds
+// the categorical columns of `cat_mask` (bit d = column d): there the term of
+// r2 is eta_d * [x_d != X_id], the Hamming indicator, in place of the squared
+// difference. MP stays the derivative with respect to r2 either way.
+template <bool MIXED>
 __global__ void k_gp_cross_cov(const double* __restrict__ X,  // (N, D)
                                const double* __restrict__ eta,  // (D)
                                double scale, const double* __restrict__ x,  // (B, D)
                                int64_t N, int64_t D, int64_t B,
                                double* __restrict__ K,    // (B, N)
-                               double* __restrict__ MP) {  // (B, N) scale*m52'(r2)
+                               double* __restrict__ MP,   // (B, N) scale*m52'(r2)
+                               uint64_t cat_mask) {
     __shared__ double xs[64];
     __shared__ double et[64];
     const int64_t b = blockIdx.y;
@@ -65,6 +70,12 @@ __global__ void k_gp_cross_cov(const double* __restrict__ X,  // (N, D)
     double r2 = 0.0;
     for (int64_t d = 0; d < D; ++d) {
         const double diff = xs[d] - X[i * D + d];
+        if constexpr (MIXED) {
+            if ((cat_mask >> d) & 1) {
+                r2 += et[d] * (diff != 0.0 ? 1.0 : 0.0);
+                continue;
+            }
+        }
         r2 += et[d] * diff * diff;
     }
     const double u = sqrt(5.0 * r2);
@@ -74,21 +85,36 @@ __global__ void k_gp_cross_cov(const double* __restrict__ X,  // (N, D)
 }
 
 // One fitted GP on the device: X (N, D), alpha = Cinv @ y (N), the explicit
-// inverse Cinv (N, N), eta (D) and the kernel scale.
+// inverse Cinv (N, N), eta (D), the kernel scale and the categorical columns
+// of the search space (bit d = column d; all GPs of a session share it).
 struct GpRef {
     const double *X, *alpha, *cinv, *eta;
     double scale;
+    uint64_t cat_mask;
 };
+
+// Throws, with `who` in front, unless 1 <= D <= 64 and `cat_mask` names
+// columns below D only.
+static void gp_check_dims(const std::string& who, int64_t D, uint64_t cat_mask) {
+    if (D < 1 || D > 64) throw std::runtime_error(who + ": need 1 <= D <= 64");
+    if (D < 64 && (cat_mask >> D) != 0)
+        throw std::runtime_error(who + ": cat_mask has a bit at or above D");
+}
+
+// Whether column d is categorical.
+__host__ __device__ __forceinline__ bool gp_is_cat(uint64_t cat_mask, int d) {
+    return (cat_mask >> d) & 1;
+}
 
 // The GPs behind four pointer vectors and their scales into out[0 .. n), n
 // returned. Throws, with `who` in front, unless there is one entry per GP,
-// lo <= n <= hi, 1 <= D <= 64 and N >= 1.
+// lo <= n <= hi, 1 <= D <= 64, cat_mask within D and N >= 1.
 static int gp_make_refs(const std::string& who, const std::vector<int64_t>& X_ptrs,
                         const std::vector<int64_t>& alpha_ptrs,
                         const std::vector<int64_t>& cinv_ptrs,
                         const std::vector<int64_t>& eta_ptrs,
                         const std::vector<double>& scales, int lo, int hi,
-                        int64_t N, int64_t D, GpRef* out) {
+                        int64_t N, int64_t D, uint64_t cat_mask, GpRef* out) {
     const size_t n = scales.size();
     if (n < (size_t)lo || n > (size_t)hi)
         throw std::runtime_error(who + ": need " + std::to_string(lo) +
@@ -96,25 +122,31 @@ static int gp_make_refs(const std::string& who, const std::vector<int64_t>& X_pt
     if (X_ptrs.size() != n || alpha_ptrs.size() != n || cinv_ptrs.size() != n ||
         eta_ptrs.size() != n)
         throw std::runtime_error(who + ": one pointer per GP");
-    if (D < 1 || D > 64) throw std::runtime_error(who + ": need 1 <= D <= 64");
+    gp_check_dims(who, D, cat_mask);
     if (N < 1) throw std::runtime_error(who + ": N < 1");
     for (size_t i = 0; i < n; ++i)
         out[i] = GpRef{reinterpret_cast<const double*>(X_ptrs[i]),
                        reinterpret_cast<const double*>(alpha_ptrs[i]),
                        reinterpret_cast<const double*>(cinv_ptrs[i]),
-                       reinterpret_cast<const double*>(eta_ptrs[i]), scales[i]};
+                       reinterpret_cast<const double*>(eta_ptrs[i]), scales[i],
+                       cat_mask};
     return (int)n;
 }
 
 // Enqueue K and MP (bc, N) of the bc <= GP_GRID_Y_MAX candidates x, then
 // V(bc, N) = K(bc, N) @ Cinv(N, N): a column-major dgemm with the symmetric
-// Cinv — C^T = Cinv^T @ K^T == Cinv @ K^T.
+// Cinv — C^T = Cinv^T @ K^T == Cinv @ K^T. An all-continuous space runs the
+// unmixed cross-covariance instantiation.
 static void gp_enqueue_kv(hipStream_t st, rocblas_handle blas, const GpRef& gp,
                           const double* x, int64_t bc, int64_t N, int64_t D,
                           double* K, double* MP, double* V) {
     const dim3 grid((unsigned)((N + GP_BLOCK - 1) / GP_BLOCK), (unsigned)bc);
-    hipLaunchKernelGGL(k_gp_cross_cov, grid, dim3(GP_BLOCK), 0, st, gp.X, gp.eta,
-                       gp.scale, x, N, D, bc, K, MP);
+    if (gp.cat_mask != 0)
+        hipLaunchKernelGGL(k_gp_cross_cov<true>, grid, dim3(GP_BLOCK), 0, st, gp.X,
+                           gp.eta, gp.scale, x, N, D, bc, K, MP, gp.cat_mask);
+    else
+        hipLaunchKernelGGL(k_gp_cross_cov<false>, grid, dim3(GP_BLOCK), 0, st, gp.X,
+                           gp.eta, gp.scale, x, N, D, bc, K, MP, gp.cat_mask);
     const double one = 1.0, zero = 0.0;
     ROCBLAS_CHECK(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_none,
                                 (rocblas_int)N, (rocblas_int)bc, (rocblas_int)N,

@@ -29,11 +29,12 @@ PYBIND11_MODULE(_hipcore, m) {
         .def(py::init<const std::vector<int64_t>&, const std::vector<int64_t>&,
                       const std::vector<int64_t>&, const std::vector<int64_t>&,
                       const std::vector<double>&, const std::vector<double>&,
-                      int64_t, int64_t, double, int64_t>(),
+                      int64_t, int64_t, double, int64_t, uint64_t>(),
              py::arg("X_ptrs"), py::arg("alpha_ptrs"), py::arg("cinv_ptrs"),
              py::arg("eta_ptrs"), py::arg("scales"), py::arg("thresholds"),
              py::arg("N"), py::arg("D"), py::arg("stab_noise"),
-             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES)
+             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES,
+             py::arg("cat_mask") = (uint64_t)0)
         .def("n_chunks", &GpConstraintSet::n_chunks, py::arg("B"),
              py::arg("with_grad"))
         .def("n_splits", &GpConstraintSet::n_splits, py::arg("bc"))
@@ -41,21 +42,24 @@ PYBIND11_MODULE(_hipcore, m) {
     m.attr("GP_FEAS_MAX_C") = py::int_(FEAS_MAX_C);
     py::class_<GpLogEiSession>(m, "GpLogEiSession")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                      double, double, double>(),
+                      double, double, double, uint64_t>(),
              py::arg("X_ptr"), py::arg("alpha_ptr"), py::arg("cinv_ptr"),
              py::arg("eta_ptr"), py::arg("N"), py::arg("D"), py::arg("scale"),
-             py::arg("stab_noise"), py::arg("threshold"))
+             py::arg("stab_noise"), py::arg("threshold"),
+             py::arg("cat_mask") = (uint64_t)0)
         .def("eval", &GpLogEiSession::eval, py::arg("x"), py::arg("with_grad"),
              py::arg("constraints") = py::none());
     py::class_<GpLogEhviSession>(m, "GpLogEhviSession")
         .def(py::init<const std::vector<int64_t>&, const std::vector<int64_t>&,
                       const std::vector<int64_t>&, const std::vector<int64_t>&,
                       const std::vector<double>&, int64_t, int64_t, double,
-                      const arr_f64&, const arr_f64&, const arr_f64&, int64_t>(),
+                      const arr_f64&, const arr_f64&, const arr_f64&, int64_t,
+                      uint64_t>(),
              py::arg("X_ptrs"), py::arg("alpha_ptrs"), py::arg("cinv_ptrs"),
              py::arg("eta_ptrs"), py::arg("scales"), py::arg("N"), py::arg("D"),
              py::arg("stab_noise"), py::arg("eps"), py::arg("lo"), py::arg("iv"),
-             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES)
+             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES,
+             py::arg("cat_mask") = (uint64_t)0)
         .def("n_chunks", &GpLogEhviSession::n_chunks, py::arg("B"),
              py::arg("with_grad"))
         .def("eval", &GpLogEhviSession::eval, py::arg("x"), py::arg("with_grad"),
