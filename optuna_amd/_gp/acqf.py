@@ -33,34 +33,51 @@ _EPS = 1e-12  # zero eps makes gradients NaN
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 # Below this z the two terms of z*Phi(z)+phi(z) cancel; switch to the erfcx form.
 _TAIL_Z = -1.0
+# Below this z the erfcx form's 1 + m is taken from its asymptotic series (four
+# terms). The same cut and term count as LOGEI_SERIES_Z in _hip/csrc/gp_logei.h,
+# where the two figures behind them are written down.
+_SERIES_Z = -256.0
 
 
 def standard_logei(z: "torch.Tensor") -> "torch.Tensor":
     """log E_{x~N(0,1)}[max(0, x+z)] = log(z*Phi(z) + phi(z)), tail-stable.
 
-    Two algebraically-equivalent evaluations selected by ``torch.where``:
+    Three algebraically-equivalent evaluations selected by ``torch.where``:
 
-    * right half (z >= _TAIL_Z): the textbook sum, whose terms are the same
+    * right (z >= _TAIL_Z): the textbook sum, whose terms are the same
       order of magnitude there, logged directly;
-    * left half: factor phi(z) out first.  Since Phi(z) = phi(z) *
-      sqrt(pi/2) * erfcx(-z/sqrt(2)), the whole expectation is
-      phi(z) * (1 + sqrt(pi/2) * z * erfcx(-z/sqrt(2))) and its log is the
-      log-density plus a log1p of a quantity in (-1, 0] — no cancellation
-      however deep the tail.
+    * left (_SERIES_Z <= z < _TAIL_Z): factor phi(z) out first.  Since
+      Phi(z) = phi(z) * sqrt(pi/2) * erfcx(-z/sqrt(2)), the whole expectation
+      is phi(z) * (1 + m) with m = sqrt(pi/2) * z * erfcx(-z/sqrt(2)) in
+      (-1, 0], and its log is the log-density plus log1p(m). 1 + m behaves
+      like 1/z^2, so the value loses about z^2 ulps of log1p's result and the
+      derivative taken by autograd about z^2 ulps of its own: harmless down to
+      the cut (7e-12), not below it (the derivative is off by 4e-7 at
+      z = -1e5, and log1p(-1) = -inf at z = -1e8);
+    * far left (z < _SERIES_Z): 1 + m from its asymptotic series
+      1/z^2 - 3/z^4 + 15/z^6 - 105/z^8, which at the cut is within 2^-53 of
+      it and has no cancellation at all, in the value or under autograd.
 
-    Both branches are evaluated on range-clamped copies of ``z`` so the
-    inactive branch can neither overflow nor poison gradients through where().
+    Every branch is evaluated on a range-clamped copy of ``z`` so the
+    inactive branches can neither overflow nor poison gradients through where().
     """
     inv_sqrt2 = math.sqrt(0.5)
     zr = z.clamp(min=_TAIL_Z - 0.5)
     phi_r = torch.exp(-0.5 * zr * zr - _HALF_LOG_2PI)
     right = torch.log(zr * torch.special.ndtr(zr) + phi_r)
 
-    zl = z.clamp(max=_TAIL_Z + 0.5)
+    zl = z.clamp(min=_SERIES_Z - 1.0, max=_TAIL_Z + 0.5)
     scaled_mills = math.sqrt(0.5 * math.pi) * zl * torch.special.erfcx(-zl * inv_sqrt2)
     left = (-0.5 * zl * zl - _HALF_LOG_2PI) + torch.log1p(scaled_mills)
 
-    return torch.where(z >= _TAIL_Z, right, left)
+    zt = z.clamp(max=_SERIES_Z + 1.0)
+    u = 1.0 / (zt * zt)
+    series = u * (1.0 - u * (3.0 - u * (15.0 - 105.0 * u)))
+    far_left = (-0.5 * zt * zt - _HALF_LOG_2PI) + torch.log(series)
+
+    return torch.where(
+        z >= _TAIL_Z, right, torch.where(z >= _SERIES_Z, left, far_left)
+    )
 
 
 def logei(mean: "torch.Tensor", var: "torch.Tensor", f0: float) -> "torch.Tensor":

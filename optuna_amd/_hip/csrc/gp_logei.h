@@ -5,8 +5,9 @@
 // (posterior GEMMs, erfc branches, autograd); here one kernel computes the
 // cross-covariances, a rocBLAS dgemm applies the explicit covariance inverse
 // and one kernel finalizes mean/var, the tail-stable log-EI and its CLOSED
-// FORM gradient:  df/dmean = exp(logPhi(z) - logg(z))/s,
-// df/dvar = exp(logphi(z) - logg(z))/(2 var),
+// FORM gradient:  df/dmean = (Phi(z)/h(z))/s,
+// df/dvar = (phi(z)/h(z))/(2 var), 0 where the clamp on the raw variance is
+// active (d_logei_weights has the two ratios),
 // dk_i/dx_d = scale * m52'(r2_i) * 2 eta_d (x_d - X_id) — so
 // grad_d = 2 eta_d (x_d * sum_i c_i - sum_i c_i X_id) with
 // c_i = (w_m alpha_i - 2 w_v V_i) * scale * m52'(r2_i). On a categorical
@@ -24,15 +25,55 @@ __device__ __forceinline__ double d_log_ndtr(double z) {
     return -0.5 * z * z + log(0.5 * erfcx(-z * 0.7071067811865476));
 }
 
-// log(z*Phi(z) + phi(z)), the same two-branch form as the host standard_logei.
+// For z < -1 the expectation is h(z) = z Phi(z) + phi(z) = phi(z) (1 + m) with
+// m = sqrt(pi/2) z erfcx(-z/sqrt 2) in (-1, 0). 1 + m behaves like 1/z^2, so
+// forming it from m loses about z^2 ulps. Below LOGEI_SERIES_Z it comes from
+// the asymptotic series
+//   1 + m = 1/z^2 - 3/z^4 + 15/z^6 - 105/z^8 + 945/z^10 - ...
+// cut after four terms. The two numbers go together
+// (mpmath, 80 digits; scripts/gen_gp_logei_golden.py prints both figures):
+//   * at z = -256 the four terms differ from 1 + m by 5.1e-17 of it, under
+//     2^-53 = 1.1e-16, and by less further out (three terms: 3.7e-13);
+//   * just above the cut the direct form is off by about z^2 2^-53 = 7.3e-12,
+//     1e5 times under the gradient tolerance 1e-6 where a factor of 100 is
+//     asked for, which |z| <= 9490 would still give.
+constexpr double LOGEI_SERIES_Z = -256.0;
+
+// 1 + m for z < LOGEI_SERIES_Z: the four terms.
+__device__ __forceinline__ double d_logei_series(double z) {
+    const double u = 1.0 / (z * z);
+    return u * (1.0 - u * (3.0 - u * (15.0 - 105.0 * u)));
+}
+
+// log(z*Phi(z) + phi(z)), the same three-branch form as the host standard_logei.
 __device__ __forceinline__ double d_standard_logei(double z) {
     constexpr double HALF_LOG_2PI = 0.9189385332046727;
     if (z >= -1.0) {
         const double phi = exp(-0.5 * z * z - HALF_LOG_2PI);
         return log(z * 0.5 * erfc(-z * 0.7071067811865476) + phi);
     }
+    if (z < LOGEI_SERIES_Z)
+        return (-0.5 * z * z - HALF_LOG_2PI) + log(d_logei_series(z));
     const double mills = 1.2533141373155003 * z * erfcx(-z * 0.7071067811865476);
     return (-0.5 * z * z - HALF_LOG_2PI) + log1p(mills);
+}
+
+// r_m = Phi(z)/h(z) = d log h / dz and r_v = phi(z)/h(z), given logg = log h(z).
+// For z < -1 both come from erfcx and 1 + m: the log-space form subtracts two
+// numbers of size z^2/2 and has lost every digit by z = -1e8.
+__device__ __forceinline__ void d_logei_weights(double z, double logg, double* r_m,
+                                                double* r_v) {
+    constexpr double HALF_LOG_2PI = 0.9189385332046727;
+    if (z >= -1.0) {
+        *r_m = exp(d_log_ndtr(z) - logg);
+        *r_v = exp(-0.5 * z * z - HALF_LOG_2PI - logg);
+        return;
+    }
+    const double e = erfcx(-z * 0.7071067811865476);
+    const double s =
+        z < LOGEI_SERIES_Z ? d_logei_series(z) : 1.0 + 1.2533141373155003 * z * e;
+    *r_m = 1.2533141373155003 * e / s;
+    *r_v = 1.0 / s;
 }
 
 // Phase 3 (phases 1 and 2 are gp_enqueue_kv): per-candidate mean/var/log-EI (+ gradient when out_grad != null).
@@ -75,17 +116,20 @@ __global__ void k_gp_logei_final(const double* __restrict__ K,      // (B, N)
     }
     if (threadIdx.x == 0) {
         const double mean = red_a[0];
-        double var = scale - red_b[0];
-        var = (var > 0.0 ? var : 0.0) + stab_noise;
+        const double raw = scale - red_b[0];
+        // Like autograd through clamp_min(0), and like k_gp_ehvi_posterior and
+        // k_gp_logpi_finish, nothing goes through a clamped variance.
+        const bool passes = raw >= 0.0;
+        const double var = (passes ? raw : 0.0) + stab_noise;
         const double sdev = sqrt(var);
         const double z = (mean - threshold) / sdev;
         const double logg = d_standard_logei(z);
         out_f[b] = 0.5 * log(var) + logg;
         if (out_grad) {
-            constexpr double HALF_LOG_2PI = 0.9189385332046727;
-            // df/dmean and df/dvar in stable log space.
-            s_wm = exp(d_log_ndtr(z) - logg) / sdev;
-            s_wv = exp(-0.5 * z * z - HALF_LOG_2PI - logg) / (2.0 * var);
+            double r_m, r_v;
+            d_logei_weights(z, logg, &r_m, &r_v);
+            s_wm = r_m / sdev;
+            s_wv = passes ? r_v / (2.0 * var) : 0.0;
         }
     }
     if (!out_grad) return;
