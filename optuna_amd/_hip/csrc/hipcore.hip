@@ -102,8 +102,6 @@ PYBIND11_MODULE(_hipcore, m) {
         .def_property_readonly("n_rows", &TpeDeviceHistory::n_rows)
         .def("append", &TpeDeviceHistory::append, py::arg("block"))
         .def("upload_sorted", &TpeDeviceHistory::upload_sorted, py::arg("cols"))
-        .def("insert_sorted", &TpeDeviceHistory::insert_sorted, py::arg("pos"),
-             py::arg("rows"))
         .def_property_readonly("n_sorted", &TpeDeviceHistory::n_sorted)
         .def("insert_sorted_by_value", &TpeDeviceHistory::insert_sorted_by_value,
              py::arg("first_row"), py::arg("n_new"))

@@ -35,6 +35,18 @@ static void launch_mix_logpdf(hipStream_t st, const double* d_x,
                        d_part_m, d_part_s, n_chunks, S, d_out);
 }
 
+// End of a scoring call: copy the result (shape.prod() doubles at d_src) into a
+// fresh array, drain the stream and surface any launch error.
+static py::array_t<double> download_f64(hipStream_t st, const double* d_src,
+                                        std::vector<py::ssize_t> shape) {
+    py::array_t<double> out(std::move(shape));
+    HIP_CHECK(hipMemcpyAsync(out.mutable_data(), d_src, (size_t)out.size() * 8,
+                             hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    return out;
+}
+
 // Full fused path: fit one KDE on device and evaluate candidates.
 //   obs        (N, D)   observations, KDE domain
 //   sorted_pos (N, D)   column-wise ranks (row index of r-th smallest per dim)
@@ -59,7 +71,6 @@ py::array_t<double> kde_logpdf(const arr_f64& obs, const arr_i64& sorted_pos,
         sorted_pos.shape(0) != N || (N > 0 && sorted_pos.shape(1) != D))
         throw std::runtime_error("shape mismatch in kde_logpdf");
 
-    py::array_t<double> out(S);
     hipStream_t st = g_ws.get_stream();
 
     const size_t n_obs = (size_t)N * D;
@@ -109,11 +120,7 @@ py::array_t<double> kde_logpdf(const arr_f64& obs, const arr_i64& sorted_pos,
     }
     launch_mix_logpdf(st, d_x, d_xedges, d_c1, d_c2, d_c3, d_logw, d_steps,
                       d_nchoices, cat_base, K, D, S, d_out, d_scratch);
-    HIP_CHECK(hipMemcpyAsync(out.mutable_data(), d_out, S * 8,
-                             hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipGetLastError());
-    return out;
+    return download_f64(st, d_out, {S});
 }
 
 // Below estimator of a fused suggest, fitted on the host in one call (see
@@ -165,9 +172,12 @@ py::tuple tpe_below_kernels(const py::array& obs, const py::array& alow,
 // Device-resident TPE history (one per (study, search-space) on the Python side).
 //
 // The parameter table lives in HBM and grows append-only, mirroring the host
-// history (_history.py); a suggest uploads only the per-dim global sorted order
-// (i32), the subset position map, mixture weights and candidates — the big fp64
-// observation matrix never crosses PCIe again after its append.
+// history (_history.py). The per-dim global sorted order (i32) is resident too:
+// upload_sorted seeds it and insert_sorted_by_value grows it on the device
+// (score also accepts explicit columns, uploaded for that call only). A suggest
+// uploads only the subset position map, the domain, mixture weights and
+// candidates — the big fp64 observation matrix never crosses PCIe again after
+// its append.
 //
 // score() pipeline (all on one stream):
 //   1. k_compact_{count,scan,write}: per dim, order-preserving compaction of
@@ -233,6 +243,8 @@ class TpeDeviceHistory {
             (!resident_sorted && Nv > 0 && (int64_t)sorted_cols.size() != D_) ||
             (int64_t)logw.size() != K)
             throw std::runtime_error("score: shape mismatch");
+        if (Na < 0 || Na > Nv)
+            throw std::runtime_error("score: n_above exceeds the sorted index");
         if (L > 0 && ((int64_t)extras_sorted.size() != L * D_ ||
                       (int64_t)extras_sorted_idx.size() != L * D_ ||
                       extras_raw.shape(1) != D_))
@@ -299,7 +311,7 @@ class TpeDeviceHistory {
             g_ws.h2d(d_extra_idx, extras_sorted_idx.data(), (size_t)L * D_ * 4, st);
         }
 
-        if (Na > 0) {
+        if (Na > 0 && Nv > 0) {
             const int32_t* s_src = resident_sorted ? sorted_.ptr : d_sorted;
             const int64_t s_stride = resident_sorted ? sorted_cap_ : Nv;
             const dim3 grid((unsigned)n_tiles, (unsigned)D_);
@@ -341,22 +353,11 @@ class TpeDeviceHistory {
                                dim3((unsigned)S, (unsigned)D_), dim3(256), 0, st,
                                d_x, d_xedges, d_c1, d_c2, d_c3, d_logw, d_steps,
                                d_nchoices, cat_base, K, D_, d_out);
-            py::array_t<double> out({S, D_});
-            HIP_CHECK(hipMemcpyAsync(out.mutable_data(), d_out,
-                                     (size_t)S * D_ * 8, hipMemcpyDeviceToHost,
-                                     st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            HIP_CHECK(hipGetLastError());
-            return out;
+            return download_f64(st, d_out, {S, D_});
         }
         launch_mix_logpdf(st, d_x, d_xedges, d_c1, d_c2, d_c3, d_logw, d_steps,
                           d_nchoices, cat_base, K, D_, S, d_out, d_scratch);
-        py::array_t<double> out(S);
-        HIP_CHECK(hipMemcpyAsync(out.mutable_data(), d_out, S * 8,
-                                 hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipGetLastError());
-        return out;
+        return download_f64(st, d_out, {S});
     }
 
     // ---- device-resident per-dim sorted index ------------------------------
@@ -374,37 +375,6 @@ class TpeDeviceHistory {
         g_ws.end_uploads_async(st);
         n_sorted_ = Nv;
         sorted_valid_ = true;
-    }
-
-    void insert_sorted(const arr_i32& pos, const arr_i32& rows) {
-        // pos (n_new, D): FINAL indices (already offset by earlier rows of the
-        // same batch); rows (n_new, D): per-dim row ids in per-dim value order.
-        if (!sorted_valid_) throw std::runtime_error("insert_sorted before upload");
-        const int64_t n_new = pos.ndim() == 2 ? pos.shape(0) : 0;
-        if (n_new == 0) return;
-        prep_.valid = false;
-        if (pos.shape(1) != D_ || rows.shape(0) != n_new || rows.shape(1) != D_)
-            throw std::runtime_error("insert_sorted: shape mismatch");
-        hipStream_t st = g_ws.get_stream();
-        ensure_sorted_capacity(n_sorted_ + n_new, st);
-        // small staging via the workspace device buffer tail is unsafe (ensure
-        // may realloc); use a dedicated tiny upload through pinned staging.
-        const size_t n_idx = (size_t)n_new * D_;
-        WsLayout L;
-        const auto s_pos = L.add<int32_t>(n_idx), s_rows = L.add<int32_t>(n_idx);
-        char* base = g_ws.ensure_bytes(L.bytes());
-        int32_t *d_pos = s_pos.in(base), *d_rows = s_rows.in(base);
-        g_ws.begin_uploads();
-        g_ws.h2d(d_pos, pos.data(), n_idx * 4, st);
-        g_ws.h2d(d_rows, rows.data(), n_idx * 4, st);
-        hipLaunchKernelGGL(k_sorted_insert, dim3((unsigned)D_), dim3(256), 0, st,
-                           sorted_.ptr, sorted_cap_, n_sorted_, d_pos, d_rows,
-                           n_new, D_);
-        // The insert kernel reads workspace memory that a later ensure_bytes() may
-        // reallocate; drain before returning (≈ the kernel's own few µs).
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipGetLastError());
-        n_sorted_ += n_new;
     }
 
     int64_t n_sorted() const { return sorted_valid_ ? n_sorted_ : -1; }

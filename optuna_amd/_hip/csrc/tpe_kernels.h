@@ -646,41 +646,15 @@ __global__ void k_parzen_fit_table(const double* __restrict__ params,  // (n_row
 }
 
 // Incremental insert into the device-resident per-dim sorted index: one block
-// per dim; rows are inserted sequentially (positions are final indices, i.e.
-// already offset by earlier inserts of the same batch). The tail shift is a
-// block-parallel backward memmove in descending chunks: within a chunk every
-// thread reads before any thread writes; a later (lower) chunk only writes
-// cells the earlier chunk has already read.
-__global__ void k_sorted_insert(int32_t* __restrict__ cols,  // (D, cap)
-                                int64_t cap, int64_t n_sorted,
-                                const int32_t* __restrict__ pos,   // (n_new, D)
-                                const int32_t* __restrict__ rows,  // (n_new, D)
-                                int64_t n_new, int64_t D) {
-    const int64_t d = blockIdx.x;
-    int32_t* col = cols + d * cap;
-    int64_t n = n_sorted;
-    for (int64_t i = 0; i < n_new; ++i) {
-        const int64_t p = pos[i * D + d];
-        for (int64_t hi = n; hi > p; hi -= blockDim.x) {
-            const int64_t j = hi - 1 - threadIdx.x;
-            int32_t v = 0;
-            if (j >= p) v = col[j];
-            __syncthreads();
-            if (j >= p) col[j + 1] = v;
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) col[p] = rows[i * D + d];
-        __syncthreads();
-        ++n;
-    }
-}
-
-// Same insert without staged positions: the kernel reads each new row's value
+// per dim; rows are inserted sequentially. The kernel reads each new row's value
 // from the resident table and finds its slot itself with an upper-bound binary
 // search through params[col[j]*D+d] (ties go after equal values and rows are
-// inserted in row order — the host rule side="right"). Row ids are kernel
-// arguments, so nothing is uploaded and the workspace is not touched; stream
-// order alone sequences it against later scoring kernels.
+// inserted in row order — the host rule side="right"). The tail shift is a
+// block-parallel backward memmove in descending chunks: within a chunk every
+// thread reads before any thread writes; a later (lower) chunk only writes
+// cells the earlier chunk has already read. Row ids are kernel arguments, so
+// nothing is uploaded and the workspace is not touched; stream order alone
+// sequences it against later scoring kernels.
 __global__ void k_sorted_insert_by_value(int32_t* __restrict__ cols,  // (D, cap)
                                          int64_t cap, int64_t n_sorted,
                                          const double* __restrict__ params,

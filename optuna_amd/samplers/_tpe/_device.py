@@ -4,8 +4,9 @@ Device modes:
 
 * **Resident history** (the fast path): each (study, search-space) keeps a
   ``TpeDeviceHistory`` whose parameter table lives in HBM and grows append-only
-  in lockstep with the host mirror (``_history.py``). A suggest uploads only the
-  per-dim sorted order (i32), a subset position map, the mixture weights and the
+  in lockstep with the host mirror (``_history.py``). The per-dim sorted order
+  (i32) is resident too and grows on the device with each tell. A suggest
+  uploads only a subset position map, the domain, the mixture weights and the
   24 candidates — the fp64 observation matrix never crosses PCIe again. Subset
   compaction, the K1 fit and the K2 scoring all run on device.
 * **Fused suggest** (`fused_eligible`): for joint scoring over numerical dims the
@@ -293,7 +294,7 @@ class FusedRequest(NamedTuple):
 
 def _space_domains(
     space: dict[str, BaseDistribution],
-) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
     """(is_log, alow, ahigh, steps, n_choices) per dim, KDE domain.
 
     Step-discretized dims widen the domain by half a step on each side before

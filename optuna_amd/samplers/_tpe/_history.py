@@ -61,16 +61,11 @@ class _SpaceCache:
         # directly (contiguous per-dim prefixes, no per-suggest restack/cast).
         # The host index is maintained lazily: `append` only records the new
         # valid rows, and the accessors below (`sorted_vals`, `sorted_rows`,
-        # `_insert_log`, `_n_sorted`) replay the backlog first. A suggest that
-        # runs on the device-resident index never pays the per-dim tail shifts.
+        # `_n_sorted`) replay the backlog first. A suggest that runs on the
+        # device-resident index never pays the per-dim tail shifts.
         self._n_sorted_host = 0
         self._vals_buf = [np.empty(64, dtype=np.float64) for _ in self.names]
         self._rows_buf = [np.empty(64, dtype=np.int32) for _ in self.names]
-        # Insert log for the device-resident sorted index: per append, the
-        # FINAL insert position and row id per dim (consumed by the GPU mirror
-        # so each suggest replays O(new) inserts instead of re-uploading the
-        # whole (Nv, D) order).
-        self._insert_log_host: list[tuple[np.ndarray, np.ndarray]] = []
         self._pending: list[np.ndarray] = []  # valid rows per append, unflushed
         # Non-flushing counters: valid rows so far, and the invalid row ids
         # (rows whose trial lacks a parameter of the space), ascending.
@@ -100,11 +95,6 @@ class _SpaceCache:
     def _n_sorted(self) -> int:
         self._flush()
         return self._n_sorted_host
-
-    @property
-    def _insert_log(self) -> list[tuple[np.ndarray, np.ndarray]]:
-        self._flush()
-        return self._insert_log_host
 
     @property
     def n_invalid(self) -> int:
@@ -159,7 +149,7 @@ class _SpaceCache:
 
     def _flush(self) -> None:
         """Bring the host sorted index up to date, one recorded append at a
-        time (so the arrays and the insert log equal eager maintenance)."""
+        time (so the arrays equal eager maintenance)."""
         if self._pending:
             pending, self._pending = self._pending, []
             for new_rows in pending:
@@ -177,8 +167,6 @@ class _SpaceCache:
                 rb[:n] = self._rows_buf[c][:n]
                 self._vals_buf[c] = vb
                 self._rows_buf[c] = rb
-        log_pos = np.empty((m, len(self.names)), dtype=np.int32)
-        log_rows = np.empty((m, len(self.names)), dtype=np.int32)
         for c in range(len(self.names)):
             vb = self._vals_buf[c]
             rb = self._rows_buf[c]
@@ -201,8 +189,6 @@ class _SpaceCache:
                 rb[i + 1 : n + 1] = si[:tail]
                 vb[i] = vals[0]
                 rb[i] = new_rows[0]
-                log_pos[0, c] = i
-                log_rows[0, c] = new_rows[0]
             else:
                 order = np.argsort(vals, kind="stable")
                 vals_sorted = vals[order]
@@ -212,11 +198,6 @@ class _SpaceCache:
                 merged_r = np.insert(rb[:n], pos, rows_sorted)
                 vb[: n + m] = merged_v
                 rb[: n + m] = merged_r
-                # Final indices: np.insert places the j-th inserted value at
-                # pos[j] + j in the merged array.
-                log_pos[:, c] = pos + np.arange(m)
-                log_rows[:, c] = rows_sorted
-        self._insert_log_host.append((log_pos, log_rows))
         self._n_sorted_host = n + m
 
     _shift_scratch: tuple[np.ndarray, np.ndarray] | None = None

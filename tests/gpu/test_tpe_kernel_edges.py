@@ -252,12 +252,15 @@ def test_resident_sorted_index(core, kind) -> None:
         table = np.array(cache.params[n_rows:], dtype=np.float64)
         table[np.isnan(block).any(axis=1)] = 0.0  # never indexed: not in the sorted order
         hist.append(np.ascontiguousarray(table))
-        n_rows += len(block)
         if step == 0:
             hist.upload_sorted(list(cache.sorted_rows))
         else:
-            log_pos, log_rows = cache._insert_log[-1]
-            hist.insert_sorted(np.ascontiguousarray(log_pos), np.ascontiguousarray(log_rows))
+            # One insert per run of valid rows, as the sampler's mirror does.
+            ok = np.concatenate([[False], cache.valid[n_rows:], [False]])
+            edges = np.flatnonzero(ok[1:] != ok[:-1])
+            for first, end in zip(edges[::2], edges[1::2]):
+                hist.insert_sorted_by_value(n_rows + int(first), int(end - first))
+        n_rows += len(block)
         valid = np.nonzero(cache.valid)[0]
         assert hist.n_sorted == len(valid) == cache._n_sorted
 
@@ -269,6 +272,21 @@ def test_resident_sorted_index(core, kind) -> None:
                           len(valid), a)
         np.testing.assert_array_equal(resident, explicit)
         _check(resident, mixture_logpdf(obs=np.array(cache.params)[valid], **a))
+
+
+def test_score_refuses_n_above_beyond_the_index(core) -> None:
+    """A host-side argument check: it throws before anything is launched, and
+    a correct call on the same history then scores as usual."""
+    obs = np.array([[-1.0, 2.0], [3.0, -4.0], [0.5, 0.25]])
+    x = np.random.RandomState(5).uniform(-5, 5, (4, 2))
+    pos = np.arange(3, dtype=np.int32)
+    hist = _table(core, obs)
+    hist.upload_sorted(_sorted_cols(obs))
+    bad = _float2_args(_mix_weights(default_ramp(4)), x)
+    with pytest.raises(RuntimeError, match="n_above"):
+        _score(hist, [], pos, 4, bad)
+    a = _float2_args(_mix_weights(default_ramp(3)), x)
+    _check(_score(hist, [], pos, 3, a), mixture_logpdf(obs=obs, **a))
 
 
 # ---------------------------------------------------------------------------

@@ -256,10 +256,6 @@ def test_lazy_index_equals_eager() -> None:
         valid = np.nonzero(lazy.valid)[0]
         order = valid[np.argsort(lazy.params[valid, c], kind="stable")]
         np.testing.assert_array_equal(lazy.sorted_rows[c], order)
-    assert len(lazy._insert_log) == len(eager._insert_log)
-    for (lp, lr), (ep, er) in zip(lazy._insert_log, eager._insert_log):
-        np.testing.assert_array_equal(lp, ep)
-        np.testing.assert_array_equal(lr, er)
 
 
 # ---------------------------------------------------------------------------
