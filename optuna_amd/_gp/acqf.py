@@ -37,6 +37,10 @@ _TAIL_Z = -1.0
 # terms). The same cut and term count as LOGEI_SERIES_Z in _hip/csrc/gp_logei.h,
 # where the two figures behind them are written down.
 _SERIES_Z = -256.0
+# What the fused qLogEI session takes: QLOGEI_MAX_R running trials and
+# QLOGEI_MAX_Q draws in _hip/csrc/gp_qlogei.h.
+_QLOGEI_MAX_R = 64
+_QLOGEI_MAX_Q = 1024
 
 
 def standard_logei(z: "torch.Tensor") -> "torch.Tensor":
@@ -341,7 +345,7 @@ class LogEI(_FusedEntryPoints, BaseAcquisitionFunc):
         )
 
 
-class qLogEI(BaseAcquisitionFunc):
+class qLogEI(_FusedEntryPoints, BaseAcquisitionFunc):
     def __init__(
         self,
         gpr: GPRegressor,
@@ -370,6 +374,60 @@ class qLogEI(BaseAcquisitionFunc):
 
     def eval_acqf(self, x: "torch.Tensor") -> "torch.Tensor":
         return _mean_max_log_utility(self.compute_per_sample_log_utility(x))
+
+    # ---- fused K5 device path -------------------------------------------------------
+    # A study with two or more workers has running trials at every suggest, so
+    # this, not LogEI, is what a parallel single-objective study evaluates. The
+    # session takes the base GP as the LogEI session does, and from the
+    # conditioned regressor the running points, V_r, the Cholesky factor of
+    # the running rows' posterior covariance, its solve against the fantasies'
+    # deviations and the QMC normals of the candidate column. The fantasies
+    # themselves enter only through their best improvement per draw. Taken for
+    # up to 64 running trials and 1024 draws; anything else keeps the torch
+    # path above, as qLogCEI always does.
+
+    def _build_fused_session(self):
+        cond = self._cond_gpr
+        gpr = cond._gpr
+        n_draws, n_running = cond._fantasy_samples.shape
+        if (
+            self._device is None
+            or np.isneginf(self._threshold)
+            or not _device_ready(gpr)
+            or n_running > _QLOGEI_MAX_R
+            or n_draws > _QLOGEI_MAX_Q
+        ):
+            return None
+        core = _fused_core()
+        if core is None:
+            return None
+        best_fantasy = (cond._fantasy_samples.amax(dim=-1) - self._threshold).clamp_min(_EPS)
+        # V_r is the transpose of a contiguous (R, N) tensor: column-major (N, R).
+        running = [
+            cond._X_running.contiguous(),
+            cond._V_r.transpose(-2, -1).contiguous(),
+            cond._cov_rr_post_chol.contiguous(),
+            cond._cov_rr_post_inv_delta_r.contiguous(),
+        ]
+        # After the copies above: _device_tensors synchronises with torch's stream.
+        self._fused_refs = _device_tensors([gpr]) + [running]
+        (X_ptr,), (alpha_ptr,), (cinv_ptr,), (eta_ptr,) = _pointers(self._fused_refs[:4])
+        return core.GpQLogEiSession(
+            X_ptr,
+            alpha_ptr,
+            cinv_ptr,
+            eta_ptr,
+            int(gpr._X_train.shape[0]),
+            int(gpr._X_train.shape[1]),
+            float(gpr.kernel_scale.item()),
+            float(cond._stabilizing_noise),
+            float(self._threshold),
+            *[t.data_ptr() for t in running],
+            int(n_running),
+            cond._fixed_samples_x.cpu().numpy(),
+            best_fantasy.cpu().numpy(),
+            cat_mask=_cat_mask(gpr._is_categorical),
+        )
 
 
 class LogPI(BaseAcquisitionFunc):

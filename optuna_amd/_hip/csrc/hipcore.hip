@@ -7,6 +7,7 @@
 #include "gp_feasibility.h"
 #include "gp_logei.h"
 #include "gp_ehvi.h"
+#include "gp_qlogei.h"
 
 #include "mo_host.h"
 #include "mo_rank.h"
@@ -49,6 +50,20 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("cat_mask") = (uint64_t)0)
         .def("eval", &GpLogEiSession::eval, py::arg("x"), py::arg("with_grad"),
              py::arg("constraints") = py::none());
+    py::class_<GpQLogEiSession>(m, "GpQLogEiSession")
+        .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                      double, double, double, int64_t, int64_t, int64_t, int64_t,
+                      int64_t, const arr_f64&, const arr_f64&, int64_t, uint64_t>(),
+             py::arg("X_ptr"), py::arg("alpha_ptr"), py::arg("cinv_ptr"),
+             py::arg("eta_ptr"), py::arg("N"), py::arg("D"), py::arg("scale"),
+             py::arg("stab_noise"), py::arg("threshold"), py::arg("Xr_ptr"),
+             py::arg("Vr_ptr"), py::arg("L_ptr"), py::arg("W_ptr"), py::arg("R"),
+             py::arg("z"), py::arg("m"),
+             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES,
+             py::arg("cat_mask") = (uint64_t)0)
+        .def("n_chunks", &GpQLogEiSession::n_chunks, py::arg("B"))
+        .def("n_splits", &GpQLogEiSession::n_splits, py::arg("bc"))
+        .def("eval", &GpQLogEiSession::eval, py::arg("x"), py::arg("with_grad"));
     py::class_<GpLogEhviSession>(m, "GpLogEhviSession")
         .def(py::init<const std::vector<int64_t>&, const std::vector<int64_t>&,
                       const std::vector<int64_t>&, const std::vector<int64_t>&,
