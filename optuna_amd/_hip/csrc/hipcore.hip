@@ -112,6 +112,7 @@ PYBIND11_MODULE(_hipcore, m) {
           py::arg("alow"), py::arg("ahigh"), py::arg("consider_endpoints"),
           py::arg("consider_magic_clip"), py::arg("active"));
     tpe_draw_py::register_functions(m, (size_t)FUSED_MAX_BELOW);
+    tpe_ledger_py::register_functions(m);
     py::class_<TpeDeviceHistory>(m, "TpeDeviceHistory")
         .def(py::init<int64_t>(), py::arg("dims"))
         .def_property_readonly("n_rows", &TpeDeviceHistory::n_rows)
@@ -127,6 +128,12 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("n_above"), py::arg("logw") = arr_f64(),
              py::arg("w_num") = 0, py::arg("w_start") = 1.0,
              py::arg("w_step") = 0.0, py::arg("log_total") = 0.0,
+             py::arg("prior_weight") = 1.0,
+             py::arg("consider_endpoints") = false,
+             py::arg("magic_clip") = true)
+        .def("fused_advance", &TpeDeviceHistory::fused_advance, py::arg("ledger"),
+             py::arg("n_below"), py::arg("valid"), py::arg("invalid_rows"),
+             py::arg("block"), py::arg("first_row"), py::arg("n_valid"),
              py::arg("prior_weight") = 1.0,
              py::arg("consider_endpoints") = false,
              py::arg("magic_clip") = true)

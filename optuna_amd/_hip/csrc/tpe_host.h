@@ -7,6 +7,7 @@
 #include "tpe_draw_bind.h"
 #include "tpe_fused_kernels.h"
 #include "tpe_kernels.h"
+#include "tpe_ledger_bind.h"
 
 // d_scratch must hold 2 * mix_n_chunks(K) * S doubles (may alias nothing else).
 static void launch_mix_logpdf(hipStream_t st, const double* d_x,
@@ -197,20 +198,12 @@ class TpeDeviceHistory {
             throw std::runtime_error("append: block must be (n_new, D)");
         const int64_t n_new = block.shape(0);
         if (n_new == 0) return;
-        prep_.valid = false;
         hipStream_t st = g_ws.get_stream();
-        if (n_ + n_new > capacity_) {
-            const int64_t new_cap = std::max<int64_t>(1024, (n_ + n_new) * 2);
-            params_.grow_preserving((size_t)new_cap * D_, 1, (size_t)n_ * D_, st);
-            capacity_ = new_cap;
-        }
         g_ws.begin_uploads();
-        g_ws.h2d(params_.ptr + (size_t)n_ * D_, block.data(),
-                 (size_t)n_new * D_ * sizeof(double), st);
+        append_rows(block.data(), n_new, st);
         // No stream sync: the table write is stream-ordered before any later
         // kernel on this stream; staging reuse is guarded by the upload event.
         g_ws.end_uploads_async(st);
-        n_ += n_new;
     }
 
     py::array_t<double> score(const std::vector<arr_i32>& sorted_cols,  // D × (Nv,)
@@ -544,7 +537,136 @@ class TpeDeviceHistory {
         return py::make_tuple(best, x_raw, out);
     }
 
+    // Everything between a tell and the above-set fit of a fused suggest in
+    // one call, for a history whose every row is a feasible complete trial
+    // (the ledger holds them all): what the sampler otherwise does through
+    // split, append, insert_sorted_by_value, excluded_rows,
+    // default_weight_ramp and fused_prepare. On the one stream, in this order:
+    // the block of new rows is appended, each run of valid new rows is
+    // inserted into the resident index, the ledger gives the below rows, the
+    // exclusion list and the default ramp are built and the fit is launched
+    // as by fused_prepare. The block's DMA and the exclusion list's share one
+    // upload batch, closed once behind the second.
+    //   n_below      size of the below set asked for (gamma of the history)
+    //   valid        (n_rows + n_new,) bool, the space's validity column
+    //   invalid_rows ascending rows of that column that are false
+    //   block        (n_new, D) KDE-domain rows first_row.., n_new <= 64
+    //   n_valid      number of true entries of `valid` (checked against the
+    //                resident index)
+    // Returns (below_rows i64, excl i32, n_below_valid, n_above, w_num,
+    // w_start, w_step, log_total, launched). When the exclusion list or the
+    // below set exceeds a fused limit, no fit is launched and `launched` is
+    // false; the table and the index are up to date all the same. The
+    // exclusion limit is held against n_below_rows + n_invalid, the bound
+    // fused_eligible uses, so that both routes decide alike.
+    py::tuple fused_advance(const tpe_ledger::TpeSplitLedger& ledger,
+                            int64_t n_below, const py::array& valid,
+                            const arr_i32& invalid_rows, const arr_f64& block,
+                            int64_t first_row, int64_t n_valid,
+                            double prior_weight, bool consider_endpoints,
+                            bool magic_clip) {
+        const std::string w("fused_advance");
+        if (!sorted_valid_) throw std::runtime_error(w + " before upload_sorted");
+        if (!domain_.ptr) throw std::runtime_error(w + " before set_domain");
+        if (has_categorical_)
+            throw std::runtime_error(w + ": categorical dims unsupported");
+        if (block.ndim() != 2 || block.shape(1) != D_)
+            throw std::runtime_error(w + ": block must be (n_new, D)");
+        const int64_t n_new = block.shape(0);
+        const int64_t n_total = n_ + n_new;
+        if (first_row != n_ || n_new > ADVANCE_MAX_NEW || n_below < 0)
+            throw std::runtime_error(w + ": rows out of step with the table");
+        if (!py::isinstance<py::array_t<bool>>(valid) || valid.ndim() != 1 ||
+            !(valid.flags() & py::array::c_style) || valid.shape(0) != n_total)
+            throw std::runtime_error(
+                w + ": valid must be a contiguous bool column of the table");
+        const bool* p_valid = static_cast<const bool*>(valid.data());
+        const int64_t n_inv = invalid_rows.size();
+        const int32_t* p_inv = invalid_rows.data();
+        for (int64_t e = 0; e < n_inv; ++e)
+            if (p_inv[e] < 0 || p_inv[e] >= n_total || p_valid[p_inv[e]] ||
+                (e > 0 && p_inv[e] <= p_inv[e - 1]))
+                throw std::runtime_error(w + ": invalid_rows must be the sorted "
+                                             "rows the space does not cover");
+        int64_t new_valid = 0;
+        for (int64_t r = n_; r < n_total; ++r) new_valid += p_valid[r] ? 1 : 0;
+        if ((int64_t)ledger.size() != n_total || n_valid + n_inv != n_total ||
+            n_sorted_ + new_valid != n_valid)
+            throw std::runtime_error(w + ": ledger, table and index disagree");
+
+        hipStream_t st = g_ws.get_stream();
+        g_ws.begin_uploads();
+        bool batch_open = false;
+        if (n_new > 0) {
+            append_rows(block.data(), n_new, st);
+            batch_open = true;
+            // One insert per run of valid rows, as the sampler's mirror does.
+            for (int64_t r = first_row; r < n_total;) {
+                if (!p_valid[r]) {
+                    ++r;
+                    continue;
+                }
+                int64_t e = r;
+                while (e < n_total && p_valid[e]) ++e;
+                insert_sorted_by_value(r, e - r);
+                r = e;
+            }
+        }
+
+        const int64_t nb = std::min<int64_t>(n_below, n_total);
+        py::array_t<int64_t> below_rows((py::ssize_t)nb);
+        int64_t* p_below = below_rows.mutable_data();
+        ledger.below((size_t)nb, p_below);
+        int64_t n_below_valid = 0;
+        for (int64_t i = 0; i < nb; ++i) {
+            if (p_below[i] < 0 || p_below[i] >= n_total)
+                throw std::runtime_error(w + ": ledger row outside the table");
+            n_below_valid += p_valid[p_below[i]] ? 1 : 0;
+        }
+        const int64_t n_above = n_valid - n_below_valid;
+        const bool fits = nb + n_inv <= FUSED_MAX_EXCL &&
+                          n_below_valid + 1 <= FUSED_MAX_BELOW;
+        std::vector<int32_t>& ex = advance_excl_;
+        ex.resize((size_t)(nb + n_inv));
+        const int64_t E = (int64_t)tpe_ledger::exclusion_list(
+            p_below, (size_t)nb, p_inv, (size_t)n_inv, ex.data());
+        arr_i32 excl((py::ssize_t)E);
+        std::copy(ex.begin(), ex.begin() + E, excl.mutable_data());
+        const tpe_ledger::WeightRamp ramp =
+            tpe_ledger::default_weight_ramp(n_above, prior_weight);
+        bool launched = false;
+        if (fits) {
+            const arr_f64 no_logw;
+            check_fit_args("fused_advance", excl, n_above, no_logw);
+            launch_fit(excl, n_above, no_logw, ramp.num, ramp.start, ramp.step,
+                       ramp.log_total, prior_weight, consider_endpoints,
+                       magic_clip, /*guard_staging=*/true);
+            launched = true;
+            batch_open = batch_open && E == 0;  // closed behind the excl DMA
+        }
+        if (batch_open) g_ws.end_uploads_async(st);
+        return py::make_tuple(below_rows, excl, n_below_valid, n_above, ramp.num,
+                              ramp.start, ramp.step, ramp.log_total, launched);
+    }
+
+    // Rows one fused_advance call may bring: beyond it the sequential device
+    // insert is slower than a bulk upload of the index.
+    static constexpr int64_t ADVANCE_MAX_NEW = 64;
+
   private:
+    // Appends (n_new, D) KDE-domain rows inside the caller's upload batch.
+    void append_rows(const double* rows, int64_t n_new, hipStream_t st) {
+        prep_.valid = false;
+        if (n_ + n_new > capacity_) {
+            const int64_t new_cap = std::max<int64_t>(1024, (n_ + n_new) * 2);
+            params_.grow_preserving((size_t)new_cap * D_, 1, (size_t)n_ * D_, st);
+            capacity_ = new_cap;
+        }
+        g_ws.h2d(params_.ptr + (size_t)n_ * D_, rows,
+                 (size_t)n_new * D_ * sizeof(double), st);
+        n_ += n_new;
+    }
+
     // What the coefficients in coef_ were fitted from. They stay usable only
     // while the table, the index, the domain and every fit argument are the
     // same; every mutator of those clears `valid`.
@@ -781,4 +903,5 @@ class TpeDeviceHistory {
     DeviceBuffer<char> coef_;
     PreparedFit prep_;
     tpe_draw_py::HostDraw draw_;  // host half of fused_draw_score
+    std::vector<int32_t> advance_excl_;  // scratch of fused_advance
 };

@@ -41,6 +41,24 @@ Device modes:
   numpy's own ufuncs, called on packed arrays (`csrc/tpe_draw_host.h`,
   `csrc/tpe_draw_bind.h`). `OPTUNA_AMD_TPE_NATIVE_DRAW=0`, an extension without
   the entry or a scipy without those capsules keep the three-call route.
+* **Native advance route** (`advance_fused_resident`, the default from a
+  space's second suggest on while the history keeps a native split ledger, see
+  `_history.py`): everything between the tell and the scoring call is one
+  native call, `TpeDeviceHistory.fused_advance`, in place of `split`, `sync`,
+  `excluded_rows`, `default_weight_ramp` and `fused_prepare`. It appends the
+  rows not yet on the device (their KDE-domain block is still built here, so
+  the table holds numpy's `log`), inserts them into the resident index, reads
+  the below rows from the ledger, builds the exclusion list and the default
+  ramp and launches the above-set fit: O(log N + n_below) host work and no
+  O(N) array. The mirror records the fit as prepared, so the scoring call
+  finds it as after `prepare_fused`. Covered: single objective, every row a
+  feasible complete trial in trial-number order, default estimator and
+  weights, joint scoring, no constant-liar row, no categorical dim, at most 64
+  new rows, an above set the device would take anyway. Everything else, the
+  first suggest of a space, an extension without the entry and
+  `OPTUNA_AMD_TPE_NATIVE_HISTORY=0` keep the separate steps. When a fused
+  limit does not hold the call only brings the mirror up to date and the
+  suggest goes on from behind `split`.
 * **Stateless scoring** (`kde_logpdf`): used by golden tests and the
   constant-liar path (whose observation set includes rows not in the table).
 
@@ -64,6 +82,7 @@ from optuna_amd.distributions import (
     IntDistribution,
 )
 from optuna_amd.samplers._tpe import _truncnorm_np as _tn
+from optuna_amd.samplers._tpe._history import native_history_enabled
 from optuna_amd.samplers._tpe.parzen import _NumericalSpace, _to_param_domain
 
 
@@ -279,6 +298,15 @@ class DrawRequest(NamedTuple):
     u: np.ndarray  # (S,) random_sample draw of the kernel choice
     q: np.ndarray  # (S, D) uniform draw of the quantile
     entry: object  # what native_below gave: the history's fused_draw_score
+
+
+class Advance(NamedTuple):
+    """What the native advance route (``advance_fused_resident``) found."""
+
+    below_rows: np.ndarray  # table rows of the below set, ascending
+    n_below_valid: int  # of them, rows valid for the space
+    n_above: int  # valid rows outside the below set
+    launched: bool  # the fit runs; False: a fused limit does not hold
 
 
 class FusedRequest(NamedTuple):
@@ -530,6 +558,57 @@ class _SpaceDeviceMirror:
         )
         self._prepared = (key, fit_args, below_rows, weights)
 
+    def advance_fused(
+        self,
+        cache: "_SpaceCache",
+        entry,
+        ledger,
+        n_below: int,
+        consider_endpoints: bool,
+        consider_magic_clip: bool,
+        prior_weight: float,
+    ) -> Advance | None:
+        """``sync`` and ``prepare_fused`` with the default ramp, behind a
+        split read from ``ledger``, in one native call (``entry``, the
+        history's ``fused_advance``). None, with nothing done, when the
+        mirror is not one step behind a resident index or the above set may
+        be too small for the device."""
+        n_total = cache._n_rows
+        first = self._n_appended
+        if (
+            self._rows_sorted_synced != first
+            or n_total - first > 64
+            or cache.n_valid - n_below < DEVICE_MIN_KERNELS
+        ):
+            return None
+        block = np.array(cache.params[first:], dtype=np.float64)
+        if n_total > first and self._is_log.any():
+            with np.errstate(invalid="ignore", divide="ignore"):
+                block[:, self._is_log] = np.log(block[:, self._is_log])
+        if len(cache._invalid_arr) != len(cache._invalid_rows):
+            cache._invalid_arr = np.asarray(cache._invalid_rows, dtype=np.int32)
+        prior_weight = float(prior_weight)
+        out = entry(
+            ledger, n_below, cache.valid, cache._invalid_arr, block, first, cache.n_valid,
+            prior_weight, consider_endpoints, consider_magic_clip,
+        )
+        self._n_appended = self._rows_sorted_synced = n_total
+        below_rows, excl, n_below_valid, n_above = out[:4]
+        launched = bool(out[8])
+        if launched:
+            # As prepare_fused leaves it: the scoring call of this suggest
+            # takes these arguments over as they are.
+            fit_args = (
+                excl, n_above, _EMPTY_F64, *out[4:8], prior_weight, consider_endpoints,
+                consider_magic_clip,
+            )
+            key = self._suggest_key(
+                cache, below_rows, n_above, None, consider_endpoints, consider_magic_clip,
+                prior_weight,
+            )
+            self._prepared = (key, fit_args, below_rows, None)
+        return Advance(below_rows, n_below_valid, n_above, launched)
+
     @staticmethod
     def _suggest_key(
         cache, below_rows, n_above, weights, consider_endpoints, consider_magic_clip, prior_weight
@@ -666,6 +745,41 @@ def prepare_fused_resident(
     _mirror_of(cache).prepare_fused(
         cache, below_rows, n_above, weights, consider_endpoints, consider_magic_clip,
         prior_weight,
+    )
+
+
+def advance_fused_resident(
+    cache: "_SpaceCache",
+    ledger,
+    n_below: int,
+    consider_endpoints: bool,
+    consider_magic_clip: bool,
+    prior_weight: float = 1.0,
+) -> Advance | None:
+    """Native advance route (module docstring) for a suggest whose history
+    keeps the split ledger ``ledger`` and whose sampler is the default
+    estimator with default weights, scoring jointly without constant-liar
+    rows. None when the route is not taken; the caller then splits and
+    prepares as usual. The entry is resolved once per space cache, behind the
+    first suggest (which makes the device mirror and uploads the index)."""
+    entry = getattr(cache, "_native_advance_entry", _UNRESOLVED)
+    if entry is _UNRESOLVED:
+        mirror = getattr(cache, "_device_mirror", None)
+        if mirror is None:
+            return None
+        entry = None
+        if (
+            native_history_enabled()
+            and _hip.is_available()
+            and bool(cache.dists)
+            and not any(isinstance(d, CategoricalDistribution) for d in cache.dists)
+        ):
+            entry = getattr(mirror._hist, "fused_advance", None)
+        cache._native_advance_entry = entry  # type: ignore[attr-defined]
+    if entry is None or not fused_enabled():
+        return None
+    return cache._device_mirror.advance_fused(  # type: ignore[attr-defined]
+        cache, entry, ledger, n_below, consider_endpoints, consider_magic_clip, prior_weight
     )
 
 

@@ -18,13 +18,27 @@ per-suggest host→device traffic of the full history.
 
 Finished trials are immutable (storage contract, storages/_base.py), which is
 what makes the append-only mirror sound.
+
+While every mirrored row of a single-objective study is a feasible COMPLETE
+trial with a value, appended in trial-number order, the value-sorted list of
+those rows lives in a native ``TpeSplitLedger`` (``_hip/csrc/tpe_ledger_host.h``)
+when the extension offers one: a tell is then a binary search and a memmove
+instead of two ``np.insert`` over the history, and the fused suggest reads its
+below rows from the ledger inside one native call (``_device.py``, native
+advance route). ``_comp_vals`` / ``_comp_rows`` export the ledger on demand, so
+``split`` is the same code with or without it. The first pruned, infeasible,
+NaN-valued or out-of-order trial hands the list back to numpy for good.
+``OPTUNA_AMD_TPE_NATIVE_HISTORY=0`` keeps numpy from the start.
 """
 from __future__ import annotations
 
-from typing import TYPE_CHECKING, Sequence
+import math
+import os
+from typing import TYPE_CHECKING, Any, Sequence
 
 import numpy as np
 
+from optuna_amd import _hip
 from optuna_amd.distributions import BaseDistribution
 from optuna_amd.study._study_direction import StudyDirection
 from optuna_amd.trial import FrozenTrial, TrialState
@@ -34,6 +48,22 @@ if TYPE_CHECKING:
     from optuna_amd.study import Study
 
 _CHUNK = 4096  # growth granularity of the SoA arrays
+
+_COMPLETE = int(TrialState.COMPLETE)
+
+
+def native_history_enabled() -> bool:
+    """``OPTUNA_AMD_TPE_NATIVE_HISTORY=0`` keeps the value-sorted complete list
+    in numpy and the fused suggest on its separate host steps (A/B runs)."""
+    return os.environ.get("OPTUNA_AMD_TPE_NATIVE_HISTORY", "1") != "0"
+
+
+def _native_ledger_class() -> Any:
+    """The extension's ``TpeSplitLedger``, or None (switched off, no device,
+    or an extension without it). Asked once per history."""
+    if not native_history_enabled() or not _hip.is_available():
+        return None
+    return getattr(_hip.get(), "TpeSplitLedger", None)
 
 
 class _SpaceCache:
@@ -228,9 +258,16 @@ class _TpeHistory:
         # Incrementally-sorted feasible-complete rows by objective value (single-
         # objective minimize fast path for split(); ties keep row order, matching
         # a stable argsort).
-        self._comp_vals = np.empty(0, dtype=np.float64)
-        self._comp_rows = np.empty(0, dtype=np.int64)
+        self._comp_vals_arr = np.empty(0, dtype=np.float64)
+        self._comp_rows_arr = np.empty(0, dtype=np.int64)
         self._comp_cache_valid = True
+        # Native storage of that list while the history is covered (module
+        # docstring): keys are `_ledger_sign` times the value, so that a
+        # maximize study's ledger is ordered as its split orders it.
+        self._ledger: Any = None
+        self._ledger_sign = 1.0
+        self._ledger_resolved = False
+        self._comp_export: tuple[int, np.ndarray, np.ndarray] | None = None
         # Split memo: independent-mode TPE (e.g. multi-objective) runs one
         # _sample per dimension within a single suggest; the history is
         # unchanged between them, so the (rows, gamma) split — including the
@@ -272,10 +309,162 @@ class _TpeHistory:
     def trials(self) -> list[FrozenTrial]:
         return self._trials
 
+    # ---- value-sorted complete list --------------------------------------------------
+
+    @property
+    def _comp_vals(self) -> np.ndarray:
+        return self._comp_arrays()[0]
+
+    @_comp_vals.setter
+    def _comp_vals(self, arr: np.ndarray) -> None:
+        self._comp_vals_arr = arr
+
+    @property
+    def _comp_rows(self) -> np.ndarray:
+        return self._comp_arrays()[1]
+
+    @_comp_rows.setter
+    def _comp_rows(self, arr: np.ndarray) -> None:
+        self._comp_rows_arr = arr
+
+    def _comp_arrays(self) -> tuple[np.ndarray, np.ndarray]:
+        """(values ascending, their rows; ties in row order): numpy's own
+        arrays, or an export of the ledger, kept until the ledger grows."""
+        ledger = self._ledger
+        if ledger is None:
+            return self._comp_vals_arr, self._comp_rows_arr
+        memo = self._comp_export
+        if memo is None or memo[0] != len(ledger):
+            if self._ledger_sign > 0:
+                vals, rows = ledger.export()
+            else:
+                # The list is kept by value whatever the direction; a maximize
+                # ledger is ordered by -value, so sort the column instead
+                # (the ledger's rows are the first len(ledger) of the table,
+                # every one a feasible complete trial).
+                assert self._values_buf is not None
+                col = self._values_buf[: len(ledger), 0]
+                rows = np.argsort(col, kind="stable")
+                vals = col[rows]
+            memo = self._comp_export = (len(ledger), vals, rows)
+        return memo[1], memo[2]
+
+    def _drop_ledger(self) -> None:
+        """Hands the list back to numpy, for good."""
+        if self._ledger is not None:
+            self._comp_vals_arr, self._comp_rows_arr = self._comp_arrays()
+            self._ledger = None
+            self._comp_export = None
+
+    def ledger_for(self, study: "Study") -> Any:
+        """The ledger when it orders every mirrored row as ``split`` would for
+        this study (single objective, the ledger's direction, the flags of the
+        fast paths intact), else None."""
+        ledger = self._ledger
+        if ledger is None or not (self._rows_number_ascending and self._comp_cache_valid):
+            return None
+        directions = study.directions
+        if len(directions) != 1:
+            return None
+        sign = -1.0 if directions[0] == StudyDirection.MAXIMIZE else 1.0
+        return ledger if sign == self._ledger_sign else None
+
+    def complement_rows(self, below: np.ndarray) -> np.ndarray:
+        """The rows outside ``below`` in row order: ``split``'s above set when
+        rows are in trial-number order."""
+        mask = np.ones(self._m_n, dtype=bool)
+        mask[below] = False
+        return np.nonzero(mask)[0]
+
+    def _grow(self, need: int) -> None:
+        cap = max(2 * self._m_cap, need)
+        base_m = self._m_n
+        for attr in (
+            "_numbers_buf",
+            "_states_buf",
+            "_violations_buf",
+            "_pruned_step_buf",
+            "_pruned_value_buf",
+            "_has_intermediate_buf",
+            "_values_buf",
+        ):
+            old = getattr(self, attr)
+            grown = np.empty((cap,) + old.shape[1:], dtype=old.dtype)
+            grown[:base_m] = old[:base_m]
+            setattr(self, attr, grown)
+        self._m_cap = cap
+
+    def _append_one(self, t: FrozenTrial) -> None:
+        """``update`` for one new trial of a history with a ledger: the same
+        row, written as scalars, and one ledger insert."""
+        row = self._m_n
+        number = t.number
+        state = int(t.state)
+        value = math.nan
+        if t.values is not None and len(t.values) == 1:
+            value = float(t.values[0])
+        violation = 0.0
+        constraints = t.system_attrs.get("constraints")
+        if constraints is not None:
+            violation = float(sum(v for v in constraints if v > 0))
+        self._seen.add(t._trial_id)
+        if row and number <= self._numbers_buf[row - 1]:
+            self._rows_number_ascending = False
+        if self._values_buf is None:
+            self._values_buf = np.empty((self._m_cap, 1), dtype=np.float64)
+        if row + 1 > self._m_cap:
+            self._grow(row + 1)
+        self._numbers_buf[row] = number
+        self._states_buf[row] = state
+        self._values_buf[row, 0] = value
+        self._violations_buf[row] = violation
+        if t.intermediate_values:
+            step, iv = max(t.intermediate_values.items())
+            self._pruned_step_buf[row] = step
+            self._pruned_value_buf[row] = iv
+            self._has_intermediate_buf[row] = True
+        else:
+            self._pruned_step_buf[row] = math.nan
+            self._pruned_value_buf[row] = math.nan
+            self._has_intermediate_buf[row] = False
+        self._m_n = row + 1
+        self._trials.append(t)
+        new = (t,)
+        for cache in self._spaces.values():
+            cache.append(new)
+
+        if state == _COMPLETE and violation <= 0 and value == value:
+            if self._rows_number_ascending:
+                self._ledger.insert(row, self._ledger_sign * value)
+                return
+            self._drop_ledger()
+            self._insert_complete(
+                np.array([row], dtype=np.int64), np.array([value], dtype=np.float64)
+            )
+            return
+        self._drop_ledger()
+        if state == _COMPLETE and violation <= 0:
+            self._comp_cache_valid = False  # a NaN value, as in update
+
+    def _insert_complete(self, rs: np.ndarray, vs: np.ndarray) -> None:
+        # side="right": equal values keep insertion (= row) order,
+        # matching a stable argsort over the full column.
+        pos = np.searchsorted(self._comp_vals_arr, vs, side="right")
+        self._comp_vals_arr = np.insert(self._comp_vals_arr, pos, vs)
+        self._comp_rows_arr = np.insert(self._comp_rows_arr, pos, rs)
+
     def update(
-        self, finished: Sequence[FrozenTrial], n_objectives: int, delta: bool = False
+        self,
+        finished: Sequence[FrozenTrial],
+        n_objectives: int,
+        delta: bool = False,
+        maximize: bool = False,
     ) -> None:
         """Append trials not yet mirrored.
+
+        ``maximize`` is the direction of a single-objective study; it only
+        orders the native ledger (module docstring) and is read when the first
+        trials arrive.
 
         With ``delta=True``, ``finished`` is a partial list (e.g. from
         ``InMemoryStorage.get_finished_trials_since``) and is deduped directly.
@@ -303,6 +492,15 @@ class _TpeHistory:
         if not new:
             return
         n_new = len(new)
+        if not self._ledger_resolved:
+            self._ledger_resolved = True
+            cls = _native_ledger_class() if n_objectives == 1 else None
+            if cls is not None:
+                self._ledger = cls()
+                self._ledger_sign = -1.0 if maximize else 1.0
+        if n_new == 1 and self._ledger is not None and n_objectives == 1:
+            self._append_one(new[0])
+            return
         numbers = np.fromiter((t.number for t in new), dtype=np.int64, count=n_new)
         states = np.fromiter((int(t.state) for t in new), dtype=np.int8, count=n_new)
         values = np.full((n_new, n_objectives), np.nan, dtype=np.float64)
@@ -332,21 +530,7 @@ class _TpeHistory:
         if self._values_buf is None:
             self._values_buf = np.empty((self._m_cap, n_objectives), dtype=np.float64)
         if base_m + n_new > self._m_cap:
-            cap = max(2 * self._m_cap, base_m + n_new)
-            for attr in (
-                "_numbers_buf",
-                "_states_buf",
-                "_violations_buf",
-                "_pruned_step_buf",
-                "_pruned_value_buf",
-                "_has_intermediate_buf",
-                "_values_buf",
-            ):
-                old = getattr(self, attr)
-                grown = np.empty((cap,) + old.shape[1:], dtype=old.dtype)
-                grown[:base_m] = old[:base_m]
-                setattr(self, attr, grown)
-            self._m_cap = cap
+            self._grow(base_m + n_new)
         self._numbers_buf[base_m : base_m + n_new] = numbers
         self._states_buf[base_m : base_m + n_new] = states
         self._values_buf[base_m : base_m + n_new] = values
@@ -358,6 +542,23 @@ class _TpeHistory:
         self._trials.extend(new)
         for cache in self._spaces.values():
             cache.append(new)
+
+        if self._ledger is not None:
+            # Stays only while every row is covered (module docstring).
+            covered = (
+                n_objectives == 1
+                and self._rows_number_ascending
+                and bool(np.all(states == _COMPLETE))
+                and not np.any(violations > 0)
+                and not np.any(np.isnan(values[:, 0]))
+            )
+            if covered:
+                self._ledger.insert_many(
+                    np.arange(base_m, base_m + n_new, dtype=np.int64),
+                    values[:, 0] if self._ledger_sign > 0 else -values[:, 0],
+                )
+                return
+            self._drop_ledger()
 
         if self._comp_cache_valid:
             if n_objectives != 1:
@@ -373,13 +574,7 @@ class _TpeHistory:
                         self._comp_cache_valid = False
                     else:
                         order = np.argsort(vals, kind="stable")
-                        vs = vals[order]
-                        rs = (base + fc)[order]
-                        # side="right": equal values keep insertion (= row) order,
-                        # matching a stable argsort over the full column.
-                        pos = np.searchsorted(self._comp_vals, vs, side="right")
-                        self._comp_vals = np.insert(self._comp_vals, pos, vs)
-                        self._comp_rows = np.insert(self._comp_rows, pos, rs)
+                        self._insert_complete((base + fc)[order], vals[order])
 
     # ---- split ---------------------------------------------------------------------
 

@@ -422,6 +422,8 @@ class TPESampler(BaseSampler):
             # Same coherence rule as _count_finished: an instance-patched
             # listing (test instrumentation) must also feed the mirror, so the
             # storage-native delta API is bypassed in that case.
+            directions = study.directions
+            maximize = len(directions) == 1 and directions[0] == StudyDirection.MAXIMIZE
             delta_read = (
                 None
                 if "get_all_trials" in vars(study._storage)
@@ -430,8 +432,9 @@ class TPESampler(BaseSampler):
             if delta_read is not None:
                 history.update(
                     delta_read(study._study_id, len(history)),
-                    len(study.directions),
+                    len(directions),
                     delta=True,
+                    maximize=maximize,
                 )
             else:
                 finished = study._get_trials(
@@ -439,30 +442,20 @@ class TPESampler(BaseSampler):
                     states=(TrialState.COMPLETE, TrialState.PRUNED),
                     use_cache=True,
                 )
-                history.update(finished, len(study.directions))
+                history.update(finished, len(directions), maximize=maximize)
 
         if self._gamma is None:
             self._gamma = (
                 default_gamma if len(study.directions) <= 1 else default_gamma_multiobjective
             )
         n = len(history)
-        below_rows, above_rows = history.split(study, self._gamma(n))
+        n_below = self._gamma(n)
 
         from optuna_amd.samplers._tpe import _device
 
         # One key hash of the space per suggest; everything below takes the cache.
         cache = history.space_cache(search_space)
-        above_sel: np.ndarray | None = None
-        if per_dim:
-            # The batch is only equivalent to D independent 1-dim suggests
-            # when every trial of both subsets defines every dim — then the
-            # per-dim observation sets coincide with the joint ones.
-            above_sel = history.valid_rows(search_space, above_rows, cache)
-            below_sel_chk = history.valid_rows(search_space, below_rows, cache)
-            if len(below_sel_chk) != len(below_rows) or len(above_sel) != len(
-                above_rows
-            ):
-                return None
+        p = self._parzen_estimator_parameters
 
         # Constant-liar rows: other workers' RUNNING trials join the "above"
         # set (params shared via system attrs). As an (L, D) matrix they ride
@@ -492,51 +485,99 @@ class TPESampler(BaseSampler):
                     liar_extras = np.asarray(rows_list, dtype=np.float64)
         n_liar = 0 if liar_extras is None else len(liar_extras)
 
-        # Fused device entry (see _device.fused_eligible): the above set is
-        # addressed as the complement of the short exclusion list, so its size
-        # follows from the valid-row counter in O(n_below) and the O(N) row
-        # selection is skipped.
-        n_below_valid = int(np.count_nonzero(cache.valid[below_rows]))
-        fused = _device.fused_eligible(
-            search_space,
-            per_dim=per_dim,
-            n_liar=n_liar,
-            default_estimator=self._parzen_estimator_cls is _ParzenEstimator,
-            rows_ascending=history._rows_number_ascending,
-            n_excl=len(below_rows) + cache.n_invalid,
-            n_below_kernels=n_below_valid + 1,
-        )
-        if fused:
-            n_above = cache.n_valid - n_below_valid
+        # Native advance route (see _device.advance_fused_resident): with the
+        # history's split ledger, one native call stands for the split, the
+        # mirror sync, the exclusion list and the launch of the above-set fit.
+        advance = None
+        if (
+            not per_dim
+            and n_liar == 0
+            and self._parzen_estimator_cls is _ParzenEstimator
+            and p.weights is default_weights
+            and p.prior_weight >= 0
+        ):
+            ledger = history.ledger_for(study)
+            if ledger is not None:
+                advance = _device.advance_fused_resident(
+                    cache,
+                    ledger,
+                    n_below,
+                    p.consider_endpoints,
+                    p.consider_magic_clip,
+                    prior_weight=p.prior_weight,
+                )
+        if advance is None:
+            below_rows, above_rows = history.split(study, n_below)
         else:
-            if above_sel is None:
-                above_sel = history.valid_rows(search_space, above_rows, cache)
-            n_above = len(above_sel)
+            below_rows = advance.below_rows
+            if not advance.launched:
+                above_rows = history.complement_rows(below_rows)
+        advanced = advance is not None and advance.launched
 
-        use_device = (
-            self._parzen_estimator_cls is _ParzenEstimator
-            and _device.space_is_device_eligible(search_space)
-            and _device.device_ready(n_above + n_liar + 1)
-        )
-        fused = fused and use_device
+        above_sel: np.ndarray | None = None
+        if per_dim:
+            # The batch is only equivalent to D independent 1-dim suggests
+            # when every trial of both subsets defines every dim — then the
+            # per-dim observation sets coincide with the joint ones.
+            above_sel = history.valid_rows(search_space, above_rows, cache)
+            below_sel_chk = history.valid_rows(search_space, below_rows, cache)
+            if len(below_sel_chk) != len(below_rows) or len(above_sel) != len(
+                above_rows
+            ):
+                return None
+
         fused_weights: np.ndarray | None = None
         below_native = None
-        p = self._parzen_estimator_parameters
-        if fused:
-            # Everything the above-set fit needs is known here: launch it now
-            # so it runs on the GPU under the host work below (the below
-            # estimator and the candidate draw).
-            if p.weights is not default_weights:
-                fused_weights = self._above_weights(n_above)
-            _device.prepare_fused_resident(
-                cache,
-                below_rows,
-                n_above,
-                fused_weights,
-                p.consider_endpoints,
-                p.consider_magic_clip,
-                prior_weight=p.prior_weight,
+        if advanced:
+            # The advance call made these decisions and launched the fit.
+            assert advance is not None
+            n_below_valid = advance.n_below_valid
+            n_above = advance.n_above
+            fused = use_device = True
+        else:
+            # Fused device entry (see _device.fused_eligible): the above set
+            # is addressed as the complement of the short exclusion list, so
+            # its size follows from the valid-row counter in O(n_below) and
+            # the O(N) row selection is skipped.
+            n_below_valid = int(np.count_nonzero(cache.valid[below_rows]))
+            fused = _device.fused_eligible(
+                search_space,
+                per_dim=per_dim,
+                n_liar=n_liar,
+                default_estimator=self._parzen_estimator_cls is _ParzenEstimator,
+                rows_ascending=history._rows_number_ascending,
+                n_excl=len(below_rows) + cache.n_invalid,
+                n_below_kernels=n_below_valid + 1,
             )
+            if fused:
+                n_above = cache.n_valid - n_below_valid
+            else:
+                if above_sel is None:
+                    above_sel = history.valid_rows(search_space, above_rows, cache)
+                n_above = len(above_sel)
+
+            use_device = (
+                self._parzen_estimator_cls is _ParzenEstimator
+                and _device.space_is_device_eligible(search_space)
+                and _device.device_ready(n_above + n_liar + 1)
+            )
+            fused = fused and use_device
+        if fused:
+            if not advanced:
+                # Everything the above-set fit needs is known here: launch it
+                # now so it runs on the GPU under the host work below (the
+                # below estimator and the candidate draw).
+                if p.weights is not default_weights:
+                    fused_weights = self._above_weights(n_above)
+                _device.prepare_fused_resident(
+                    cache,
+                    below_rows,
+                    n_above,
+                    fused_weights,
+                    p.consider_endpoints,
+                    p.consider_magic_clip,
+                    prior_weight=p.prior_weight,
+                )
             # Native below route: the below estimator of a fused suggest is
             # fitted by one call into the extension instead of through numpy
             # (resolved behind the prepare call, which makes the device mirror

@@ -5,7 +5,13 @@ history, 20 float dims, 24 candidates) and takes ``time.perf_counter`` around
 every ``TpeDeviceHistory.fused_score`` call and, separately, around every
 ``fused_prepare`` call (a build without the early fit has none), every
 ``tpe_below_kernels`` call (the native fit of the below estimator; a build
-without it has none) and the whole of ``TPESampler._sample_locked``. Prints one
+without it has none) and the whole of ``TPESampler._sample_locked``. The host
+work ahead of the fit is timed too: ``_TpeHistory.update``, ``_TpeHistory.split``,
+the whole Python call ``_SpaceDeviceMirror.prepare_fused`` (which contains the
+native ``fused_prepare``) and, on a build with the native split ledger, the
+native ``fused_advance`` and the mirror's ``advance_fused`` around it;
+``host_before_fit_us`` is the median of ``update + split + (prepare_fused -
+fused_prepare)`` per step, where a step made all of those calls. Prints one
 JSON line with the median, the 10th/90th percentiles and min/max in
 microseconds, plus the suggest+tell rate of the timed steps.
 
@@ -81,7 +87,8 @@ def main() -> None:
     times: dict[str, list[float]] = {
         "fused_score": [], "fused_prepare": [], "tpe_below_kernels": [], "sample_locked": [],
         "fused_draw_score": [], "draw_below_native": [], "ppf": [], "score_fused": [],
-        "best_candidate": [],
+        "best_candidate": [], "update": [], "split": [], "prepare_fused": [],
+        "fused_advance": [], "advance_fused": [],
     }
 
     def timed(fn, bucket: list[float]):
@@ -107,6 +114,13 @@ def main() -> None:
     )
     mirror_cls = _device._SpaceDeviceMirror
     mirror_cls.score_fused = timed(mirror_cls.score_fused, times["score_fused"])
+    mirror_cls.prepare_fused = timed(mirror_cls.prepare_fused, times["prepare_fused"])
+    if hasattr(mirror_cls, "advance_fused"):
+        mirror_cls.advance_fused = timed(mirror_cls.advance_fused, times["advance_fused"])
+    from optuna_amd.samplers._tpe._history import _TpeHistory
+
+    _TpeHistory.update = timed(_TpeHistory.update, times["update"])
+    _TpeHistory.split = timed(_TpeHistory.split, times["split"])
     if hasattr(_device, "draw_below_native"):
         _device._tn.ppf = timed(_device._tn.ppf, times["ppf"])
         _device.draw_below_native = timed(
@@ -163,6 +177,12 @@ def main() -> None:
     n_scored = len(times["fused_score"]) + len(times["fused_draw_score"])
     assert n_scored == args.steps, "the fused path was not taken"
 
+    host_before_fit = None
+    parts = [times[k] for k in ("update", "split", "prepare_fused", "fused_prepare")]
+    if all(len(b) == args.steps for b in parts):
+        u, s, pf, fp = (np.asarray(b) for b in parts)
+        host_before_fit = round(float(np.median(u + s + (pf - fp))) * 1e6, 2)
+
     print(
         json.dumps(
             {
@@ -180,6 +200,12 @@ def main() -> None:
                 "ppf": _stats(times["ppf"]),
                 "score_fused": _stats(times["score_fused"]),
                 "best_candidate": _stats(times["best_candidate"]),
+                "update": _stats(times["update"]),
+                "split": _stats(times["split"]),
+                "prepare_fused": _stats(times["prepare_fused"]),
+                "fused_advance": _stats(times["fused_advance"]),
+                "advance_fused": _stats(times["advance_fused"]),
+                "host_before_fit_us": host_before_fit,
             }
         ),
         flush=True,
