@@ -122,6 +122,8 @@ PYBIND11_MODULE(_hipcore, m) {
         .def("insert_sorted_by_value", &TpeDeviceHistory::insert_sorted_by_value,
              py::arg("first_row"), py::arg("n_new"))
         .def("sorted_index", &TpeDeviceHistory::sorted_index)
+        .def("table_rows", &TpeDeviceHistory::table_rows, py::arg("first_row"),
+             py::arg("n_rows"))
         .def("set_domain", &TpeDeviceHistory::set_domain, py::arg("alow"),
              py::arg("ahigh"), py::arg("steps"), py::arg("n_choices"))
         .def("fused_prepare", &TpeDeviceHistory::fused_prepare, py::arg("excl"),
@@ -134,6 +136,15 @@ PYBIND11_MODULE(_hipcore, m) {
         .def("fused_advance", &TpeDeviceHistory::fused_advance, py::arg("ledger"),
              py::arg("n_below"), py::arg("valid"), py::arg("invalid_rows"),
              py::arg("block"), py::arg("first_row"), py::arg("n_valid"),
+             py::arg("prior_weight") = 1.0,
+             py::arg("consider_endpoints") = false,
+             py::arg("magic_clip") = true)
+        .def("fused_step", &TpeDeviceHistory::fused_step, py::arg("ledger"),
+             py::arg("n_below"), py::arg("valid"), py::arg("invalid_rows"),
+             py::arg("block"), py::arg("first_row"), py::arg("n_valid"),
+             py::arg("table"), py::arg("bw"), py::arg("u"), py::arg("q"),
+             py::arg("alow"), py::arg("ahigh"), py::arg("kinds"),
+             py::arg("lows"), py::arg("highs"), py::arg("steps"),
              py::arg("prior_weight") = 1.0,
              py::arg("consider_endpoints") = false,
              py::arg("magic_clip") = true)

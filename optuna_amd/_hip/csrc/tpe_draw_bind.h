@@ -135,14 +135,15 @@ struct HostDraw {
 };
 
 // Below rows -> observations -> fit -> choice -> quantile -> candidates.
-//   table (N, D) f64, valid (N,) bool, below_rows (m,) i64: the below set is
-//     the valid ones of below_rows, in that order
+//   table (N, D) f64, valid (N,) bool, below_rows m row numbers (a native
+//     buffer or an array's data): the below set is the valid ones of them, in
+//     that order
 //   bw (n + 1,) f64  normalised mixture weights of the below estimator
 //   u (S,), q (S, D) f64  uniforms of the choice and of the quantile
 //   alow, ahigh, lows, highs, steps (D,) f64, kinds (D,) i8
 // with_edges asks for the step-cell edges as well.
 inline void draw(HostDraw& H, const py::array& table, const py::array& valid,
-                 const py::array& below_rows, const py::array& bw,
+                 const int64_t* p_rows, py::ssize_t m, const py::array& bw,
                  const py::array& u, const py::array& q, const py::array& alow,
                  const py::array& ahigh, const py::array& kinds,
                  const py::array& lows, const py::array& highs,
@@ -151,7 +152,6 @@ inline void draw(HostDraw& H, const py::array& table, const py::array& valid,
     const tpe_draw::Ops& op = ops();
     const double* p_table = typed<double>(table, "table", 2);
     const bool* p_valid = typed<bool>(valid, "valid", 1);
-    const int64_t* p_rows = typed<int64_t>(below_rows, "below_rows", 1);
     const double* p_bw = typed<double>(bw, "bw", 1);
     const double* p_u = typed<double>(u, "u", 1);
     const double* p_q = typed<double>(q, "q", 2);
@@ -171,7 +171,6 @@ inline void draw(HostDraw& H, const py::array& table, const py::array& valid,
         if (p_kinds[c] < tpe_draw::KIND_CONT || p_kinds[c] > tpe_draw::KIND_LOG_DISC)
             throw std::runtime_error("tpe_draw: numerical dims only");
 
-    const py::ssize_t m = below_rows.shape(0);
     H.D = (size_t)D;
     H.S = (size_t)S;
     H.obs.resize((size_t)m * D);
@@ -263,7 +262,8 @@ inline void register_functions(py::module_& m, size_t max_kernels) {
                       const py::array& highs, const py::array& steps,
                       bool consider_endpoints, bool consider_magic_clip) {
             HostDraw H;
-            draw(H, table, valid, below_rows, bw, u, q, alow, ahigh, kinds, lows,
+            draw(H, table, valid, typed<int64_t>(below_rows, "below_rows", 1),
+                 below_rows.shape(0), bw, u, q, alow, ahigh, kinds, lows,
                  highs, steps, consider_endpoints, consider_magic_clip, true,
                  max_kernels);
             return py::make_tuple(copy_out(H.x_raw, H.S, H.D),

@@ -28,6 +28,12 @@
 static constexpr int FUSED_MAX_EXCL = 1024;
 static constexpr int FUSED_MAX_BELOW = 1024;
 static constexpr int FUSED_TILE = 256;
+// Exclusion lists up to this length travel as a kernel argument of the fit.
+static constexpr int FUSED_EXCL_BY_VALUE = 64;
+
+struct FusedExclArg {
+    int32_t e[FUSED_EXCL_BY_VALUE];
+};
 
 __device__ inline int excl_lower_bound(const int32_t* e, int E, int32_t row) {
     int lo = 0, hi = E;
@@ -65,6 +71,8 @@ __device__ inline void write_coeffs(double mu, double sigma, double low,
 // domain = alow | ahigh | steps | n_choices (D each). logw == nullptr means
 // the caller uploaded custom log-weights; otherwise the dim-0 blocks write the
 // default ramp (numpy linspace arithmetic: k*step + start, uncontracted).
+// excl == nullptr means the list (E <= FUSED_EXCL_BY_VALUE) is excl_arg, read
+// from the kernel-argument segment: nothing was uploaded for it.
 __global__ void k_fused_fit(const double* __restrict__ params,
                             const int32_t* __restrict__ sorted,  // (D, s_stride)
                             int64_t s_stride, int64_t Nv,
@@ -74,7 +82,8 @@ __global__ void k_fused_fit(const double* __restrict__ params,
                             double* __restrict__ c1, double* __restrict__ c2,
                             double* __restrict__ c3, double* __restrict__ logw,
                             int64_t w_num, double w_start, double w_step,
-                            double log_total, double prior_weight) {
+                            double log_total, double prior_weight,
+                            FusedExclArg excl_arg) {
     __shared__ int32_t s_excl[FUSED_MAX_EXCL];
     __shared__ int s_prev[FUSED_TILE];
     __shared__ int s_next[FUSED_TILE];
@@ -87,7 +96,11 @@ __global__ void k_fused_fit(const double* __restrict__ params,
     const double range = high - low;
     const int i = threadIdx.x;
 
-    for (int e = i; e < E; e += FUSED_TILE) s_excl[e] = excl[e];
+    if (excl) {
+        for (int e = i; e < E; e += FUSED_TILE) s_excl[e] = excl[e];
+    } else if (i < E && i < FUSED_EXCL_BY_VALUE) {  // one pass: 64 < FUSED_TILE
+        s_excl[i] = excl_arg.e[i];
+    }
     __syncthreads();
 
     const int64_t K = Na + 1;

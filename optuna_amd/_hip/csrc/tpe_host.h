@@ -188,6 +188,38 @@ py::tuple tpe_below_kernels(const py::array& obs, const py::array& alow,
 // ---------------------------------------------------------------------------
 
 class TpeDeviceHistory {
+    // The arguments of one above-set fit. The pointers are borrowed: numpy
+    // arrays of the caller, or this history's own scratch.
+    struct FitArgs {
+        const int32_t* excl = nullptr;
+        int64_t E = 0, Na = 0;
+        const double* logw = nullptr;  // custom log-weights, n_logw of them
+        int64_t n_logw = 0;            // 0: the default ramp below
+        int64_t w_num = 0;
+        double w_start = 1.0, w_step = 0.0, log_total = 0.0, prior_weight = 1.0;
+        bool consider_endpoints = false, magic_clip = true;
+    };
+
+    static FitArgs fit_args(const arr_i32& excl, int64_t n_above,
+                            const arr_f64& logw, int64_t w_num, double w_start,
+                            double w_step, double log_total, double prior_weight,
+                            bool consider_endpoints, bool magic_clip) {
+        FitArgs f;
+        f.excl = excl.data();
+        f.E = excl.size();
+        f.Na = n_above;
+        f.logw = logw.data();
+        f.n_logw = logw.size();
+        f.w_num = w_num;
+        f.w_start = w_start;
+        f.w_step = w_step;
+        f.log_total = log_total;
+        f.prior_weight = prior_weight;
+        f.consider_endpoints = consider_endpoints;
+        f.magic_clip = magic_clip;
+        return f;
+    }
+
   public:
     explicit TpeDeviceHistory(int64_t D) : D_(D) {}
 
@@ -381,13 +413,7 @@ class TpeDeviceHistory {
         prep_.valid = false;
         if (first_row < 0 || first_row + n_new > n_)
             throw std::runtime_error("insert_sorted_by_value: rows not in table");
-        hipStream_t st = g_ws.get_stream();
-        ensure_sorted_capacity(n_sorted_ + n_new, st);
-        hipLaunchKernelGGL(k_sorted_insert_by_value, dim3((unsigned)D_),
-                           dim3(256), 0, st, sorted_.ptr, sorted_cap_, n_sorted_,
-                           params_.ptr, D_, first_row, n_new);
-        HIP_CHECK(hipGetLastError());
-        n_sorted_ += n_new;
+        launch_insert(first_row, n_new, nullptr);
     }
 
     // Debug/test accessor: the resident sorted index as a (D, n_sorted) array.
@@ -400,6 +426,22 @@ class TpeDeviceHistory {
                                        sorted_.ptr, (size_t)sorted_cap_ * 4,
                                        (size_t)n_sorted_ * 4, (size_t)D_,
                                        hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return out;
+    }
+
+    // Debug/test accessor: table rows [first_row, first_row + n_rows) as an
+    // (n_rows, D) array.
+    py::array_t<double> table_rows(int64_t first_row, int64_t n_rows) {
+        if (first_row < 0 || n_rows < 0 || first_row + n_rows > n_)
+            throw std::runtime_error("table_rows: rows not in table");
+        py::array_t<double> out({n_rows, D_});
+        hipStream_t st = g_ws.get_stream();
+        if (n_rows > 0)
+            HIP_CHECK(hipMemcpyAsync(out.mutable_data(),
+                                     params_.ptr + (size_t)first_row * D_,
+                                     (size_t)n_rows * D_ * sizeof(double),
+                                     hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         return out;
     }
@@ -454,11 +496,12 @@ class TpeDeviceHistory {
                        int64_t w_num, double w_start, double w_step,
                        double log_total, double prior_weight,
                        bool consider_endpoints, bool magic_clip) {
-        check_fit_args("fused_prepare", excl, n_above, logw);
+        const FitArgs f = fit_args(excl, n_above, logw, w_num, w_start, w_step,
+                                   log_total, prior_weight, consider_endpoints,
+                                   magic_clip);
+        check_fit_args("fused_prepare", f);
         g_ws.begin_uploads();
-        launch_fit(excl, n_above, logw, w_num, w_start, w_step, log_total,
-                   prior_weight, consider_endpoints, magic_clip,
-                   /*guard_staging=*/true);
+        launch_fit(f, /*guard_staging=*/true);
     }
 
     // Returns (S,) log l - log g, or with return_parts the test/debug form
@@ -472,7 +515,10 @@ class TpeDeviceHistory {
                                     double prior_weight,
                                     bool consider_endpoints, bool magic_clip,
                                     bool return_parts) {
-        check_fit_args("fused_score", excl, n_above, logw);
+        const FitArgs f = fit_args(excl, n_above, logw, w_num, w_start, w_step,
+                                   log_total, prior_weight, consider_endpoints,
+                                   magic_clip);
+        check_fit_args("fused_score", f);
         if (x.ndim() != 2 || x.shape(1) != D_ || bmu.ndim() != 2 ||
             bmu.shape(1) != D_ || bsig.ndim() != 2 || bsig.shape(1) != D_)
             throw std::runtime_error("fused_score: shape mismatch");
@@ -488,9 +534,8 @@ class TpeDeviceHistory {
         py::array_t<double> lw(return_parts ? K : 0);
         py::array_t<double> out(return_parts ? 0 : S);
         const double* h_out = score_candidates(
-            excl, n_above, x.data(), xedges.data(), bmu.data(), bsig.data(),
-            bw.data(), S, Kb, logw, w_num, w_start, w_step, log_total,
-            prior_weight, consider_endpoints, magic_clip,
+            f, /*fit_launched=*/false, x.data(), xedges.data(), bmu.data(),
+            bsig.data(), bw.data(), S, Kb,
             return_parts ? lw.mutable_data() : nullptr);
         if (return_parts) {
             py::array_t<double> parts({(int64_t)3, S});
@@ -517,24 +562,17 @@ class TpeDeviceHistory {
                                double w_start, double w_step, double log_total,
                                double prior_weight, bool consider_endpoints,
                                bool magic_clip) {
-        check_fit_args("fused_draw_score", excl, n_above, logw);
+        const FitArgs f = fit_args(excl, n_above, logw, w_num, w_start, w_step,
+                                   log_total, prior_weight, consider_endpoints,
+                                   magic_clip);
+        check_fit_args("fused_draw_score", f);
         if (table.ndim() != 2 || table.shape(1) != D_)
             throw std::runtime_error("fused_draw_score: shape mismatch");
-        tpe_draw_py::HostDraw& H = draw_;
-        tpe_draw_py::draw(H, table, valid, below_rows, bw, u, q, alow, ahigh,
-                          kinds, lows, highs, steps, consider_endpoints,
-                          magic_clip, has_steps_, (size_t)FUSED_MAX_BELOW);
-        const int64_t S = (int64_t)H.S;
-        py::array_t<double> out(S);
-        py::array_t<double> x_raw = tpe_draw_py::copy_out(H.x_raw, H.S, H.D);
-        const double* h_out = score_candidates(
-            excl, n_above, H.x_kde.data(), H.xedges.data(), H.mus.data(),
-            H.sigmas.data(), static_cast<const double*>(bw.data()), S,
-            (int64_t)H.Kb(), logw, w_num, w_start, w_step, log_total,
-            prior_weight, consider_endpoints, magic_clip, nullptr);
-        memcpy(out.mutable_data(), h_out, (size_t)S * 8);
-        const size_t best = tpe_draw::argmax(h_out, (size_t)S);
-        return py::make_tuple(best, x_raw, out);
+        const int64_t* p_rows =
+            tpe_draw_py::typed<int64_t>(below_rows, "below_rows", 1);
+        return draw_and_score(f, /*fit_launched=*/false, table, valid, p_rows,
+                              below_rows.shape(0), bw, u, q, alow, ahigh, kinds,
+                              lows, highs, steps, /*with_values=*/true);
     }
 
     // Everything between a tell and the above-set fit of a fused suggest in
@@ -545,8 +583,11 @@ class TpeDeviceHistory {
     // the block of new rows is appended, each run of valid new rows is
     // inserted into the resident index, the ledger gives the below rows, the
     // exclusion list and the default ramp are built and the fit is launched
-    // as by fused_prepare. The block's DMA and the exclusion list's share one
-    // upload batch, closed once behind the second.
+    // as by fused_prepare. In the common step (one valid new row of at most
+    // INSERT_ROW_MAX_D dims, at most FUSED_EXCL_BY_VALUE excluded rows) the row
+    // and the list are kernel arguments: two launches, no copy, no upload
+    // batch left open. Otherwise the block's DMA and the exclusion list's
+    // share one upload batch, closed once behind the last of them.
     //   n_below      size of the below set asked for (gamma of the history)
     //   valid        (n_rows + n_new,) bool, the space's validity column
     //   invalid_rows ascending rows of that column that are false
@@ -565,7 +606,66 @@ class TpeDeviceHistory {
                             int64_t first_row, int64_t n_valid,
                             double prior_weight, bool consider_endpoints,
                             bool magic_clip) {
-        const std::string w("fused_advance");
+        const Advanced a = advance("fused_advance", ledger, n_below, valid,
+                                   invalid_rows, block, first_row, n_valid,
+                                   prior_weight, consider_endpoints, magic_clip);
+        return advance_tuple(a);
+    }
+
+    // A whole fused suggest in one call, from the tell to the chosen
+    // candidate: the advance half of fused_advance (same arguments), then,
+    // while the insert and the fit run on the GPU, the host draw of
+    // fused_draw_score (table: the host's (n_rows + n_new, D) parameter
+    // table; bw, u, q and the space arrays as there), then its device half
+    // and the arg-max. The below rows, the exclusion list and the ramp stay
+    // in this history's buffers between the halves, and the fit just launched
+    // is taken as prepared. Returns (best index, x_raw (S, D)). When the fit
+    // was not launched (a fused limit) or bw was not built for the
+    // n_below_valid + 1 below kernels found, the advance half is complete all
+    // the same and the call returns (None, what fused_advance returns): the
+    // caller goes on as behind fused_advance, with the same u and q.
+    py::tuple fused_step(const tpe_ledger::TpeSplitLedger& ledger,
+                         int64_t n_below, const py::array& valid,
+                         const arr_i32& invalid_rows, const arr_f64& block,
+                         int64_t first_row, int64_t n_valid,
+                         const py::array& table, const py::array& bw,
+                         const py::array& u, const py::array& q,
+                         const py::array& alow, const py::array& ahigh,
+                         const py::array& kinds, const py::array& lows,
+                         const py::array& highs, const py::array& steps,
+                         double prior_weight, bool consider_endpoints,
+                         bool magic_clip) {
+        if (table.ndim() != 2 || table.shape(1) != D_ || bw.ndim() != 1)
+            throw std::runtime_error("fused_step: shape mismatch");
+        const Advanced a = advance("fused_step", ledger, n_below, valid,
+                                   invalid_rows, block, first_row, n_valid,
+                                   prior_weight, consider_endpoints, magic_clip);
+        if (!a.launched || bw.shape(0) != a.n_below_valid + 1)
+            return py::make_tuple(py::none(), advance_tuple(a));
+        return draw_and_score(a.fit, /*fit_launched=*/true, table, valid,
+                              advance_below_.data(), a.nb, bw, u, q, alow, ahigh,
+                              kinds, lows, highs, steps, /*with_values=*/false);
+    }
+
+    // Rows one fused_advance call may bring: beyond it the sequential device
+    // insert is slower than a bulk upload of the index.
+    static constexpr int64_t ADVANCE_MAX_NEW = 64;
+
+  private:
+    // What the advance half found. The nb below rows are in advance_below_ and
+    // fit.excl points into advance_excl_: both hold until the next advance.
+    struct Advanced {
+        int64_t nb = 0, n_below_valid = 0;
+        FitArgs fit;
+        bool launched = false;
+    };
+
+    Advanced advance(const char* who, const tpe_ledger::TpeSplitLedger& ledger,
+                     int64_t n_below, const py::array& valid,
+                     const arr_i32& invalid_rows, const arr_f64& block,
+                     int64_t first_row, int64_t n_valid, double prior_weight,
+                     bool consider_endpoints, bool magic_clip) {
+        const std::string w(who);
         if (!sorted_valid_) throw std::runtime_error(w + " before upload_sorted");
         if (!domain_.ptr) throw std::runtime_error(w + " before set_domain");
         if (has_categorical_)
@@ -597,7 +697,14 @@ class TpeDeviceHistory {
         hipStream_t st = g_ws.get_stream();
         g_ws.begin_uploads();
         bool batch_open = false;
-        if (n_new > 0) {
+        if (n_new == 1 && D_ <= INSERT_ROW_MAX_D && p_valid[n_]) {
+            // The common step: the row travels as an argument of the insert,
+            // which stores it into the table. Nothing is copied.
+            prep_.valid = false;
+            ensure_row_capacity(1, st);
+            ++n_;
+            launch_insert(first_row, 1, block.data());
+        } else if (n_new > 0) {
             append_rows(block.data(), n_new, st);
             batch_open = true;
             // One insert per run of valid rows, as the sampler's mirror does.
@@ -613,55 +720,105 @@ class TpeDeviceHistory {
             }
         }
 
-        const int64_t nb = std::min<int64_t>(n_below, n_total);
-        py::array_t<int64_t> below_rows((py::ssize_t)nb);
-        int64_t* p_below = below_rows.mutable_data();
-        ledger.below((size_t)nb, p_below);
-        int64_t n_below_valid = 0;
-        for (int64_t i = 0; i < nb; ++i) {
+        Advanced a;
+        a.nb = std::min<int64_t>(n_below, n_total);
+        advance_below_.resize((size_t)a.nb);
+        int64_t* p_below = advance_below_.data();
+        ledger.below((size_t)a.nb, p_below);
+        for (int64_t i = 0; i < a.nb; ++i) {
             if (p_below[i] < 0 || p_below[i] >= n_total)
                 throw std::runtime_error(w + ": ledger row outside the table");
-            n_below_valid += p_valid[p_below[i]] ? 1 : 0;
+            a.n_below_valid += p_valid[p_below[i]] ? 1 : 0;
         }
-        const int64_t n_above = n_valid - n_below_valid;
-        const bool fits = nb + n_inv <= FUSED_MAX_EXCL &&
-                          n_below_valid + 1 <= FUSED_MAX_BELOW;
+        const int64_t n_above = n_valid - a.n_below_valid;
+        const bool fits = a.nb + n_inv <= FUSED_MAX_EXCL &&
+                          a.n_below_valid + 1 <= FUSED_MAX_BELOW;
         std::vector<int32_t>& ex = advance_excl_;
-        ex.resize((size_t)(nb + n_inv));
-        const int64_t E = (int64_t)tpe_ledger::exclusion_list(
-            p_below, (size_t)nb, p_inv, (size_t)n_inv, ex.data());
-        arr_i32 excl((py::ssize_t)E);
-        std::copy(ex.begin(), ex.begin() + E, excl.mutable_data());
+        ex.resize((size_t)(a.nb + n_inv));
         const tpe_ledger::WeightRamp ramp =
             tpe_ledger::default_weight_ramp(n_above, prior_weight);
-        bool launched = false;
+        FitArgs& f = a.fit;
+        f.excl = ex.data();
+        f.E = (int64_t)tpe_ledger::exclusion_list(p_below, (size_t)a.nb, p_inv,
+                                                  (size_t)n_inv, ex.data());
+        f.Na = n_above;
+        f.w_num = ramp.num;
+        f.w_start = ramp.start;
+        f.w_step = ramp.step;
+        f.log_total = ramp.log_total;
+        f.prior_weight = prior_weight;
+        f.consider_endpoints = consider_endpoints;
+        f.magic_clip = magic_clip;
         if (fits) {
-            const arr_f64 no_logw;
-            check_fit_args("fused_advance", excl, n_above, no_logw);
-            launch_fit(excl, n_above, no_logw, ramp.num, ramp.start, ramp.step,
-                       ramp.log_total, prior_weight, consider_endpoints,
-                       magic_clip, /*guard_staging=*/true);
-            launched = true;
-            batch_open = batch_open && E == 0;  // closed behind the excl DMA
+            check_fit_args(who, f);
+            // A staged exclusion list closes the batch behind its own DMA.
+            if (launch_fit(f, /*guard_staging=*/true)) batch_open = false;
+            a.launched = true;
         }
         if (batch_open) g_ws.end_uploads_async(st);
-        return py::make_tuple(below_rows, excl, n_below_valid, n_above, ramp.num,
-                              ramp.start, ramp.step, ramp.log_total, launched);
+        return a;
     }
 
-    // Rows one fused_advance call may bring: beyond it the sequential device
-    // insert is slower than a bulk upload of the index.
-    static constexpr int64_t ADVANCE_MAX_NEW = 64;
+    // The advance half's result as fused_advance returns it.
+    py::tuple advance_tuple(const Advanced& a) const {
+        py::array_t<int64_t> below_rows((py::ssize_t)a.nb);
+        std::copy(advance_below_.begin(), advance_below_.begin() + a.nb,
+                  below_rows.mutable_data());
+        arr_i32 excl((py::ssize_t)a.fit.E);
+        std::copy(a.fit.excl, a.fit.excl + a.fit.E, excl.mutable_data());
+        return py::make_tuple(below_rows, excl, a.n_below_valid, a.fit.Na,
+                              a.fit.w_num, a.fit.w_start, a.fit.w_step,
+                              a.fit.log_total, a.launched);
+    }
 
-  private:
+    // Host draw (tpe_draw_bind.h), device half, arg-max: the part that
+    // fused_draw_score and fused_step share. Returns (best, x_raw) and, with
+    // with_values, the (S,) acquisition values as a third element.
+    py::tuple draw_and_score(const FitArgs& f, bool fit_launched,
+                             const py::array& table, const py::array& valid,
+                             const int64_t* below_rows, int64_t n_rows,
+                             const py::array& bw, const py::array& u,
+                             const py::array& q, const py::array& alow,
+                             const py::array& ahigh, const py::array& kinds,
+                             const py::array& lows, const py::array& highs,
+                             const py::array& steps, bool with_values) {
+        tpe_draw_py::HostDraw& H = draw_;
+        tpe_draw_py::draw(H, table, valid, below_rows, (py::ssize_t)n_rows, bw, u,
+                          q, alow, ahigh, kinds, lows, highs, steps,
+                          f.consider_endpoints, f.magic_clip, has_steps_,
+                          (size_t)FUSED_MAX_BELOW);
+        const int64_t S = (int64_t)H.S;
+        py::array_t<double> out(with_values ? S : 0);
+        py::array_t<double> x_raw = tpe_draw_py::copy_out(H.x_raw, H.S, H.D);
+        const double* h_out = score_candidates(
+            f, fit_launched, H.x_kde.data(), H.xedges.data(), H.mus.data(),
+            H.sigmas.data(), static_cast<const double*>(bw.data()), S,
+            (int64_t)H.Kb(), nullptr);
+        const size_t best = tpe_draw::argmax(h_out, (size_t)S);
+        if (!with_values) return py::make_tuple(best, x_raw);
+        memcpy(out.mutable_data(), h_out, (size_t)S * 8);
+        return py::make_tuple(best, x_raw, out);
+    }
+
+    // Launches the insert of table rows [first_row, first_row + n_new) into
+    // the resident index. With `row` (one row of D <= INSERT_ROW_MAX_D values,
+    // already counted in n_) the kernel stores it into the table as well.
+    void launch_insert(int64_t first_row, int64_t n_new, const double* row) {
+        hipStream_t st = g_ws.get_stream();
+        ensure_sorted_capacity(n_sorted_ + n_new, st);
+        InsertRowArg arg{};
+        if (row) std::copy(row, row + D_, arg.v);
+        hipLaunchKernelGGL(k_sorted_insert_by_value, dim3((unsigned)D_),
+                           dim3(256), 0, st, sorted_.ptr, sorted_cap_, n_sorted_,
+                           params_.ptr, D_, first_row, n_new, row ? 1 : 0, arg);
+        HIP_CHECK(hipGetLastError());
+        n_sorted_ += n_new;
+    }
+
     // Appends (n_new, D) KDE-domain rows inside the caller's upload batch.
     void append_rows(const double* rows, int64_t n_new, hipStream_t st) {
         prep_.valid = false;
-        if (n_ + n_new > capacity_) {
-            const int64_t new_cap = std::max<int64_t>(1024, (n_ + n_new) * 2);
-            params_.grow_preserving((size_t)new_cap * D_, 1, (size_t)n_ * D_, st);
-            capacity_ = new_cap;
-        }
+        ensure_row_capacity(n_new, st);
         g_ws.h2d(params_.ptr + (size_t)n_ * D_, rows,
                  (size_t)n_new * D_ * sizeof(double), st);
         n_ += n_new;
@@ -679,49 +836,41 @@ class TpeDeviceHistory {
         std::vector<double> logw;  // custom log-weights, empty for the ramp
     };
 
-    void check_fit_args(const char* who, const arr_i32& excl, int64_t Na,
-                        const arr_f64& logw) const {
+    void check_fit_args(const char* who, const FitArgs& f) const {
         const std::string w(who);
         if (!sorted_valid_) throw std::runtime_error(w + " before upload_sorted");
         if (!domain_.ptr) throw std::runtime_error(w + " before set_domain");
         if (has_categorical_)
             throw std::runtime_error(w + ": categorical dims unsupported");
-        const int64_t E = excl.size();
+        const int64_t E = f.E, Na = f.Na;
         const int64_t Nv = n_sorted_;
         if (E > FUSED_MAX_EXCL || Na < 0 || Na > Nv || Na + E < Nv ||
-            (logw.size() > 0 && (int64_t)logw.size() != Na + 1))
+            (f.n_logw > 0 && f.n_logw != Na + 1))
             throw std::runtime_error(w + ": shape mismatch");
         // Strictly ascending in-table rows: keeps row - lower_bound(excl, row)
         // inside [0, n_above) for every member row.
-        const int32_t* ex = excl.data();
+        const int32_t* ex = f.excl;
         for (int64_t e = 0; e < E; ++e)
             if (ex[e] < 0 || ex[e] >= n_ || (e > 0 && ex[e] <= ex[e - 1]))
                 throw std::runtime_error(w + ": excl must be sorted table rows");
     }
 
-    // Device half of a fused suggest on checked arguments: the fall-back fit,
-    // the packed upload, k_fused_score, k_fused_merge and the stream
+    // Device half of a fused suggest on checked arguments: the fall-back fit
+    // (not looked for with fit_launched: the caller has just launched f's fit
+    // itself), the packed upload, k_fused_score, k_fused_merge and the stream
     // synchronise. Returns the merge's (3, S) result [ei | log g | log l] in
     // pinned host memory, good until the next upload batch; lw_out, if given,
     // receives the (K,) above log-weights.
-    const double* score_candidates(const arr_i32& excl, int64_t n_above,
+    const double* score_candidates(const FitArgs& f, bool fit_launched,
                                    const double* x, const double* xedges,
                                    const double* bmu, const double* bsig,
                                    const double* bw, int64_t S, int64_t Kb,
-                                   const arr_f64& logw, int64_t w_num,
-                                   double w_start, double w_step,
-                                   double log_total, double prior_weight,
-                                   bool consider_endpoints, bool magic_clip,
                                    double* lw_out) {
-        const int64_t K = n_above + 1;
+        const int64_t K = f.Na + 1;
         hipStream_t st = g_ws.get_stream();
         g_ws.begin_uploads();
-        if (!prepared_matches(excl, n_above, logw, w_num, w_start, w_step,
-                              log_total, prior_weight, consider_endpoints,
-                              magic_clip))
-            launch_fit(excl, n_above, logw, w_num, w_start, w_step, log_total,
-                       prior_weight, consider_endpoints, magic_clip,
-                       /*guard_staging=*/false);
+        if (!fit_launched && !prepared_matches(f))
+            launch_fit(f, /*guard_staging=*/false);
 
         // Packed region (one pinned slice, one DMA, same layout on device):
         //   x | bmu | bsig | bw | [xedges]
@@ -757,7 +906,7 @@ class TpeDeviceHistory {
             HIP_CHECK(hipMemcpyAsync(base, h, up_bytes, hipMemcpyHostToDevice, st));
         }
 
-        const CoefLayout C(K, D_, excl.size());
+        const CoefLayout C(K, D_, f.E);
         const double* d_logw = C.logw.in(coef_.ptr);
         const int64_t n_groups = (S + SCORE_CAND - 1) / SCORE_CAND;
         hipLaunchKernelGGL(k_fused_score,
@@ -787,23 +936,19 @@ class TpeDeviceHistory {
     }
 
     // Bit-wise comparisons throughout: equal arguments give the same fit.
-    bool prepared_matches(const arr_i32& excl, int64_t Na, const arr_f64& logw,
-                          int64_t w_num, double w_start, double w_step,
-                          double log_total, double prior_weight,
-                          bool consider_endpoints, bool magic_clip) const {
+    bool prepared_matches(const FitArgs& f) const {
         const PreparedFit& p = prep_;
-        const double a[4] = {w_start, w_step, log_total, prior_weight};
+        const double a[4] = {f.w_start, f.w_step, f.log_total, f.prior_weight};
         const double b[4] = {p.w_start, p.w_step, p.log_total, p.prior_weight};
-        return p.valid && p.n == n_ && p.n_sorted == n_sorted_ && p.Na == Na &&
-               p.w_num == w_num && memcmp(a, b, sizeof(a)) == 0 &&
-               p.consider_endpoints == consider_endpoints &&
-               p.magic_clip == magic_clip &&
-               p.excl.size() == (size_t)excl.size() &&
+        return p.valid && p.n == n_ && p.n_sorted == n_sorted_ && p.Na == f.Na &&
+               p.w_num == f.w_num && memcmp(a, b, sizeof(a)) == 0 &&
+               p.consider_endpoints == f.consider_endpoints &&
+               p.magic_clip == f.magic_clip && p.excl.size() == (size_t)f.E &&
                (p.excl.empty() ||
-                memcmp(p.excl.data(), excl.data(), p.excl.size() * 4) == 0) &&
-               p.logw.size() == (size_t)logw.size() &&
+                memcmp(p.excl.data(), f.excl, p.excl.size() * 4) == 0) &&
+               p.logw.size() == (size_t)f.n_logw &&
                (p.logw.empty() ||
-                memcmp(p.logw.data(), logw.data(), p.logw.size() * 8) == 0);
+                memcmp(p.logw.data(), f.logw, p.logw.size() * 8) == 0);
     }
 
     // coef_ = c1 | c2 | c3 (D, K each, k-major) | logw (K) | excl (E, i32).
@@ -818,37 +963,42 @@ class TpeDeviceHistory {
               excl(L.add<int32_t>(E)) {}
     };
 
-    // Upload [logw] | excl into coef_ and launch the fit behind it. The caller
-    // has opened the upload batch; with guard_staging the batch is closed with
-    // the event guard right behind the DMA (the caller does not synchronise).
-    void launch_fit(const arr_i32& excl, int64_t Na, const arr_f64& logw,
-                    int64_t w_num, double w_start, double w_step,
-                    double log_total, double prior_weight,
-                    bool consider_endpoints, bool magic_clip, bool guard_staging) {
+    // Launch the fit of f into coef_. An exclusion list of at most
+    // FUSED_EXCL_BY_VALUE rows under the default ramp is a kernel argument and
+    // nothing is uploaded (nothing downstream reads the list from coef_);
+    // otherwise [logw] | excl are uploaded into coef_ ahead of the launch. The
+    // caller has opened the upload batch; with guard_staging an upload closes
+    // it with the event guard right behind the DMA (the caller does not
+    // synchronise). Returns whether it uploaded.
+    bool launch_fit(const FitArgs& f, bool guard_staging) {
         prep_.valid = false;
         hipStream_t st = g_ws.get_stream();
-        const int64_t E = excl.size();
+        const int64_t E = f.E, Na = f.Na;
         const int64_t K = Na + 1;
         const int64_t Nv = n_sorted_;
-        const bool custom_w = logw.size() > 0;
+        const bool custom_w = f.n_logw > 0;
+        const bool by_value = !custom_w && E <= FUSED_EXCL_BY_VALUE;
         const CoefLayout C(K, D_, E);
         // Geometric growth, at least 4096 doubles.
         if (C.L.bytes() > coef_.capacity)
             coef_.reserve(std::max(4096 * sizeof(double), 2 * C.L.bytes()));
         double* d_logw = C.logw.in(coef_.ptr);
         int32_t* d_excl = C.excl.in(coef_.ptr);
+        FusedExclArg excl_arg{};
         // The upload is the tail of the coefficient layout, from logw (custom
         // weights) or from excl on; U names the same regions in the staging
         // slice.
         WsLayout U;
         const auto u_logw = U.add<double>(custom_w ? K : 0);
-        const auto u_excl = U.add<int32_t>(E);
-        if (U.bytes()) {
+        const auto u_excl = U.add<int32_t>(by_value ? 0 : E);
+        if (by_value) {
+            std::copy(f.excl, f.excl + E, excl_arg.e);
+        } else if (U.bytes()) {
             char* h = g_ws.stage(U.bytes(), st);
-            if (custom_w) memcpy(u_logw.in(h), logw.data(), (size_t)K * 8);
+            if (custom_w) memcpy(u_logw.in(h), f.logw, (size_t)K * 8);
             // For odd E the slot's padding word is uploaded too: define it.
             if (E & 1) u_excl.in(h)[E] = 0;
-            memcpy(u_excl.in(h), excl.data(), (size_t)E * 4);
+            memcpy(u_excl.in(h), f.excl, (size_t)E * 4);
             HIP_CHECK(hipMemcpyAsync(custom_w ? (void*)d_logw : (void*)d_excl, h,
                                      U.bytes(), hipMemcpyHostToDevice, st));
             if (guard_staging) g_ws.end_uploads_async(st);
@@ -856,26 +1006,34 @@ class TpeDeviceHistory {
         const int64_t n_tiles = std::max<int64_t>(1, (Nv + FUSED_TILE - 1) / FUSED_TILE);
         hipLaunchKernelGGL(k_fused_fit, dim3((unsigned)n_tiles, (unsigned)D_),
                            dim3(FUSED_TILE), 0, st, params_.ptr, sorted_.ptr,
-                           sorted_cap_, Nv, d_excl, (int)E, domain_.ptr, Na, D_,
-                           consider_endpoints ? 1 : 0, magic_clip ? 1 : 0,
-                           C.c1.in(coef_.ptr), C.c2.in(coef_.ptr),
-                           C.c3.in(coef_.ptr),
-                           custom_w ? nullptr : d_logw, w_num, w_start, w_step,
-                           log_total, prior_weight);
+                           sorted_cap_, Nv, by_value ? nullptr : d_excl, (int)E,
+                           domain_.ptr, Na, D_, f.consider_endpoints ? 1 : 0,
+                           f.magic_clip ? 1 : 0, C.c1.in(coef_.ptr),
+                           C.c2.in(coef_.ptr), C.c3.in(coef_.ptr),
+                           custom_w ? nullptr : d_logw, f.w_num, f.w_start,
+                           f.w_step, f.log_total, f.prior_weight, excl_arg);
         HIP_CHECK(hipGetLastError());
         prep_.n = n_;
         prep_.n_sorted = n_sorted_;
         prep_.Na = Na;
-        prep_.w_num = w_num;
-        prep_.w_start = w_start;
-        prep_.w_step = w_step;
-        prep_.log_total = log_total;
-        prep_.prior_weight = prior_weight;
-        prep_.consider_endpoints = consider_endpoints;
-        prep_.magic_clip = magic_clip;
-        prep_.excl.assign(excl.data(), excl.data() + E);
-        prep_.logw.assign(logw.data(), logw.data() + logw.size());
+        prep_.w_num = f.w_num;
+        prep_.w_start = f.w_start;
+        prep_.w_step = f.w_step;
+        prep_.log_total = f.log_total;
+        prep_.prior_weight = f.prior_weight;
+        prep_.consider_endpoints = f.consider_endpoints;
+        prep_.magic_clip = f.magic_clip;
+        prep_.excl.assign(f.excl, f.excl + E);
+        prep_.logw.assign(f.logw, f.logw + f.n_logw);
         prep_.valid = true;
+        return !by_value && U.bytes() > 0;
+    }
+
+    void ensure_row_capacity(int64_t n_new, hipStream_t st) {
+        if (n_ + n_new <= capacity_) return;
+        const int64_t new_cap = std::max<int64_t>(1024, (n_ + n_new) * 2);
+        params_.grow_preserving((size_t)new_cap * D_, 1, (size_t)n_ * D_, st);
+        capacity_ = new_cap;
     }
 
     void ensure_sorted_capacity(int64_t need, hipStream_t st) {
@@ -903,5 +1061,7 @@ class TpeDeviceHistory {
     DeviceBuffer<char> coef_;
     PreparedFit prep_;
     tpe_draw_py::HostDraw draw_;  // host half of fused_draw_score
-    std::vector<int32_t> advance_excl_;  // scratch of fused_advance
+    // Below rows and exclusion list of the last advance half.
+    std::vector<int64_t> advance_below_;
+    std::vector<int32_t> advance_excl_;
 };

@@ -655,17 +655,36 @@ __global__ void k_parzen_fit_table(const double* __restrict__ params,  // (n_row
 // cells the earlier chunk has already read. Row ids are kernel arguments, so
 // nothing is uploaded and the workspace is not touched; stream order alone
 // sequences it against later scoring kernels.
+//
+// With by_value (one new row of at most INSERT_ROW_MAX_D dims) the row itself
+// is a kernel argument too: block d searches with row_arg.v[d], read from the
+// kernel-argument segment, and stores it into the table, so the row needs no
+// copy ahead of the launch. The search only probes rows already indexed,
+// never the new one, so position, tie order and shift are the same.
+static constexpr int INSERT_ROW_MAX_D = 32;
+
+struct InsertRowArg {
+    double v[INSERT_ROW_MAX_D];
+};
+
 __global__ void k_sorted_insert_by_value(int32_t* __restrict__ cols,  // (D, cap)
                                          int64_t cap, int64_t n_sorted,
-                                         const double* __restrict__ params,
+                                         double* __restrict__ params,
                                          int64_t D, int64_t first_row,
-                                         int64_t n_new) {
+                                         int64_t n_new, int by_value,
+                                         InsertRowArg row_arg) {
     const int64_t d = blockIdx.x;
     int32_t* col = cols + d * cap;
     int64_t n = n_sorted;
     for (int64_t i = 0; i < n_new; ++i) {
         const int64_t row = first_row + i;
-        const double v = params[row * D + d];
+        double v;
+        if (by_value) {
+            v = row_arg.v[d];
+            if (threadIdx.x == 0) params[row * D + d] = v;
+        } else {
+            v = params[row * D + d];
+        }
         // Block-uniform search: every lane walks the same probes.
         int64_t lo = 0, hi = n;
         while (lo < hi) {

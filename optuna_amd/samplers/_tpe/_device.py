@@ -59,6 +59,21 @@ Device modes:
   `OPTUNA_AMD_TPE_NATIVE_HISTORY=0` keep the separate steps. When a fused
   limit does not hold the call only brings the mirror up to date and the
   suggest goes on from behind `split`.
+* **Native step route** (`fused_step_entry`, the default wherever the advance
+  and the draw routes are both on): the advance call and the draw call are
+  one, `TpeDeviceHistory.fused_step`, from the tell to the chosen candidate.
+  The below rows, the exclusion list and the ramp stay in native buffers
+  between the two halves, and the host draw runs while the insert and the fit
+  run on the GPU. The sampler makes the two RNG calls of the draw ahead of the
+  call, which is sound only because `fused_step_entry` has decided, from what
+  is known before the call, that the suggest ends on the draw route: the
+  advance consumes no random numbers, and every other route that would draw
+  by itself is excluded there. When the below weights passed in were built
+  for another number of below kernels than the ledger gives (rows the space
+  does not cover), the call completes the advance half, reports "not drawn"
+  and the suggest goes on through `fused_draw_score` with the same draws.
+  `OPTUNA_AMD_TPE_NATIVE_STEP=0` or an extension without the entry keep the
+  two calls.
 * **Stateless scoring** (`kde_logpdf`): used by golden tests and the
   constant-liar path (whose observation set includes rows not in the table).
 
@@ -261,6 +276,25 @@ def _bind_native_draw(core) -> bool:
     return capsules is not None and bool(bind(*capsules))
 
 
+class _DrawEntry:
+    """The one-call entries of a space's device history, as ``native_below``
+    hands them out: calling it is ``fused_draw_score``; ``step`` is the
+    history's ``fused_step`` or None. The two travel together so that whoever
+    replaces or wraps the draw entry keeps the suggest on the calls it sees,
+    and ``step`` is looked up on the history's type for the same reason: an
+    object that stands in front of a history to observe its ``fused_advance``
+    and ``fused_draw_score`` calls keeps receiving them."""
+
+    __slots__ = ("_draw", "step")
+
+    def __init__(self, hist) -> None:
+        self._draw = hist.fused_draw_score
+        self.step = hist.fused_step if getattr(type(hist), "fused_step", None) else None
+
+    def __call__(self, *args):
+        return self._draw(*args)
+
+
 def native_draw(cache: "_SpaceCache") -> bool:
     """Whether the native draw route is on for this space: ``native_below``
     then gives the one-call entry, to be passed on in a ``DrawRequest``. Off
@@ -275,11 +309,19 @@ def native_draw(cache: "_SpaceCache") -> bool:
         mirror = getattr(cache, "_device_mirror", None)
         if mirror is None:
             return False
-        entry = getattr(mirror._hist, "fused_draw_score", None)
-        if entry is not None and not _bind_native_draw(_hip.get()):
-            entry = None
+        entry = None
+        if getattr(mirror._hist, "fused_draw_score", None) is not None and _bind_native_draw(
+            _hip.get()
+        ):
+            entry = _DrawEntry(mirror._hist)
         cache._native_draw_entry = entry  # type: ignore[attr-defined]
     return entry is not None
+
+
+def native_step_enabled() -> bool:
+    """``OPTUNA_AMD_TPE_NATIVE_STEP=0`` keeps the advance and the draw of a
+    fused suggest as two native calls (A/B runs)."""
+    return os.environ.get("OPTUNA_AMD_TPE_NATIVE_STEP", "1") != "0"
 
 
 def _numerical_space_of(cache: "_SpaceCache") -> _NumericalSpace:
@@ -298,6 +340,12 @@ class DrawRequest(NamedTuple):
     u: np.ndarray  # (S,) random_sample draw of the kernel choice
     q: np.ndarray  # (S, D) uniform draw of the quantile
     entry: object  # what native_below gave: the history's fused_draw_score
+    # Native step route (``fused_step_entry``): the split is still to be read
+    # from this ledger, for a below set of n_below rows, inside the same call
+    # (entry is then that route's). below_rows and n_above are unused and
+    # below_weights are those of min(n_below, rows) + 1 kernels.
+    ledger: object = None
+    n_below: int = 0
 
 
 class Advance(NamedTuple):
@@ -558,41 +606,39 @@ class _SpaceDeviceMirror:
         )
         self._prepared = (key, fit_args, below_rows, weights)
 
-    def advance_fused(
-        self,
-        cache: "_SpaceCache",
-        entry,
-        ledger,
-        n_below: int,
-        consider_endpoints: bool,
-        consider_magic_clip: bool,
-        prior_weight: float,
-    ) -> Advance | None:
-        """``sync`` and ``prepare_fused`` with the default ramp, behind a
-        split read from ``ledger``, in one native call (``entry``, the
-        history's ``fused_advance``). None, with nothing done, when the
-        mirror is not one step behind a resident index or the above set may
-        be too small for the device."""
-        n_total = cache._n_rows
+    def can_advance(self, cache: "_SpaceCache", n_below: int) -> bool:
+        """Whether the mirror is one step (at most 64 rows) behind a resident
+        index and the above set is large enough for the device."""
         first = self._n_appended
-        if (
-            self._rows_sorted_synced != first
-            or n_total - first > 64
-            or cache.n_valid - n_below < DEVICE_MIN_KERNELS
-        ):
-            return None
+        return (
+            self._rows_sorted_synced == first
+            and cache._n_rows - first <= 64
+            and cache.n_valid - n_below >= DEVICE_MIN_KERNELS
+        )
+
+    def _advance_args(self, cache: "_SpaceCache", ledger, n_below: int) -> tuple:
+        """The leading arguments of ``fused_advance`` and ``fused_step``: the
+        rows not yet on the device as a KDE-domain block, with the validity
+        column and the rows the space does not cover."""
+        first = self._n_appended
         block = np.array(cache.params[first:], dtype=np.float64)
-        if n_total > first and self._is_log.any():
+        if cache._n_rows > first and self._is_log.any():
             with np.errstate(invalid="ignore", divide="ignore"):
                 block[:, self._is_log] = np.log(block[:, self._is_log])
         if len(cache._invalid_arr) != len(cache._invalid_rows):
             cache._invalid_arr = np.asarray(cache._invalid_rows, dtype=np.int32)
-        prior_weight = float(prior_weight)
-        out = entry(
-            ledger, n_below, cache.valid, cache._invalid_arr, block, first, cache.n_valid,
-            prior_weight, consider_endpoints, consider_magic_clip,
-        )
-        self._n_appended = self._rows_sorted_synced = n_total
+        return ledger, n_below, cache.valid, cache._invalid_arr, block, first, cache.n_valid
+
+    def _advanced(
+        self,
+        cache: "_SpaceCache",
+        out: tuple,
+        consider_endpoints: bool,
+        consider_magic_clip: bool,
+        prior_weight: float,
+    ) -> Advance:
+        """Records what the advance half returned (``out``, the tuple of
+        ``fused_advance``) as ``prepare_fused`` would."""
         below_rows, excl, n_below_valid, n_above = out[:4]
         launched = bool(out[8])
         if launched:
@@ -608,6 +654,71 @@ class _SpaceDeviceMirror:
             )
             self._prepared = (key, fit_args, below_rows, None)
         return Advance(below_rows, n_below_valid, n_above, launched)
+
+    def advance_fused(
+        self,
+        cache: "_SpaceCache",
+        entry,
+        ledger,
+        n_below: int,
+        consider_endpoints: bool,
+        consider_magic_clip: bool,
+        prior_weight: float,
+    ) -> Advance | None:
+        """``sync`` and ``prepare_fused`` with the default ramp, behind a
+        split read from ``ledger``, in one native call (``entry``, the
+        history's ``fused_advance``). None, with nothing done, when the
+        mirror is not one step behind a resident index or the above set may
+        be too small for the device."""
+        if not self.can_advance(cache, n_below):
+            return None
+        prior_weight = float(prior_weight)
+        out = entry(
+            *self._advance_args(cache, ledger, n_below),
+            prior_weight, consider_endpoints, consider_magic_clip,
+        )
+        self._n_appended = self._rows_sorted_synced = cache._n_rows
+        return self._advanced(cache, out, consider_endpoints, consider_magic_clip, prior_weight)
+
+    def step_fused(
+        self,
+        cache: "_SpaceCache",
+        req: DrawRequest,
+        consider_endpoints: bool,
+        consider_magic_clip: bool,
+        prior_weight: float,
+    ) -> tuple[int, np.ndarray] | Advance:
+        """A whole fused suggest in one native call (the history's
+        ``fused_step``): ``advance_fused`` and ``draw_score_fused`` together.
+        Only behind ``fused_step_entry``. Returns (best index, x_raw (S, D)),
+        or, when the call did not draw, what ``advance_fused`` returns."""
+        ns = _numerical_space_of(cache)
+        prior_weight = float(prior_weight)
+        # numpy's ufuncs run inside the call, as in draw_score_fused.
+        with np.errstate(divide="ignore", invalid="ignore"):
+            best, rest = req.entry(  # type: ignore[operator]
+                *self._advance_args(cache, req.ledger, req.n_below),
+                cache.params,
+                req.below_weights,
+                req.u,
+                req.q,
+                ns.adapted_lows,
+                ns.adapted_highs,
+                ns.kinds,
+                ns.lows,
+                ns.highs,
+                ns.steps,
+                prior_weight,
+                consider_endpoints,
+                consider_magic_clip,
+            )
+        self._n_appended = self._rows_sorted_synced = cache._n_rows
+        if best is None:
+            return self._advanced(
+                cache, rest, consider_endpoints, consider_magic_clip, prior_weight
+            )
+        self._prepared = None
+        return best, rest
 
     @staticmethod
     def _suggest_key(
@@ -748,20 +859,11 @@ def prepare_fused_resident(
     )
 
 
-def advance_fused_resident(
-    cache: "_SpaceCache",
-    ledger,
-    n_below: int,
-    consider_endpoints: bool,
-    consider_magic_clip: bool,
-    prior_weight: float = 1.0,
-) -> Advance | None:
-    """Native advance route (module docstring) for a suggest whose history
-    keeps the split ledger ``ledger`` and whose sampler is the default
-    estimator with default weights, scoring jointly without constant-liar
-    rows. None when the route is not taken; the caller then splits and
-    prepares as usual. The entry is resolved once per space cache, behind the
-    first suggest (which makes the device mirror and uploads the index)."""
+def _native_advance_entry(cache: "_SpaceCache"):
+    """The ``fused_advance`` of the space's device history, or None: no
+    mirror yet (the first suggest makes it and uploads the index), switched
+    off, no extension, a categorical dim or an extension without the entry.
+    Resolved once per space cache."""
     entry = getattr(cache, "_native_advance_entry", _UNRESOLVED)
     if entry is _UNRESOLVED:
         mirror = getattr(cache, "_device_mirror", None)
@@ -776,11 +878,52 @@ def advance_fused_resident(
         ):
             entry = getattr(mirror._hist, "fused_advance", None)
         cache._native_advance_entry = entry  # type: ignore[attr-defined]
-    if entry is None or not fused_enabled():
+    return entry if fused_enabled() else None
+
+
+def advance_fused_resident(
+    cache: "_SpaceCache",
+    ledger,
+    n_below: int,
+    consider_endpoints: bool,
+    consider_magic_clip: bool,
+    prior_weight: float = 1.0,
+) -> Advance | None:
+    """Native advance route (module docstring) for a suggest whose history
+    keeps the split ledger ``ledger`` and whose sampler is the default
+    estimator with default weights, scoring jointly without constant-liar
+    rows. None when the route is not taken; the caller then splits and
+    prepares as usual."""
+    entry = _native_advance_entry(cache)
+    if entry is None:
         return None
     return cache._device_mirror.advance_fused(  # type: ignore[attr-defined]
         cache, entry, ledger, n_below, consider_endpoints, consider_magic_clip, prior_weight
     )
+
+
+def fused_step_entry(cache: "_SpaceCache", n_below: int):
+    """The entry that serves the suggest ``advance_fused_resident`` would
+    serve as one native call up to the chosen candidate (native step route,
+    module docstring), or None; decided from what is known before the call.
+    An entry promises that the suggest ends on the native draw route, so its
+    two RNG draws may be made ahead of the call: the advance and the draw
+    routes are both on, ``native_below`` gives a draw entry that carries a
+    step entry, the mirror is one step behind, and the fused limits hold for
+    any below set of the size asked for (the call itself holds them against
+    the rows the ledger gives, which can only be fewer)."""
+    if not native_step_enabled() or _native_advance_entry(cache) is None:
+        return None
+    mirror = cache._device_mirror  # type: ignore[attr-defined]
+    n_below_rows = min(n_below, cache._n_rows)
+    if not (
+        mirror.can_advance(cache, n_below)
+        and n_below_rows + cache.n_invalid <= FUSED_MAX_EXCL
+        and n_below_rows + 1 <= FUSED_MAX_BELOW
+        and native_draw(cache)
+    ):
+        return None
+    return getattr(native_below(cache), "step", None)
 
 
 def score_above_resident(
@@ -794,7 +937,7 @@ def score_above_resident(
     extras: np.ndarray | None = None,
     per_dim: bool = False,
     fused: FusedRequest | DrawRequest | None = None,
-) -> np.ndarray | tuple[int, np.ndarray, np.ndarray]:
+) -> np.ndarray | tuple[int, np.ndarray, np.ndarray] | tuple[int, np.ndarray] | Advance:
     """log g(x) for candidates via the device-resident table (creates the mirror
     on first use; attached to the host space cache so lifetimes match).
     ``per_dim=True`` returns the (S, D) per-dimension 1-D mixture log-pdfs
@@ -807,8 +950,18 @@ def score_above_resident(
     With a ``DrawRequest`` as ``fused`` (see ``native_draw``) the candidates
     are drawn inside the same native call as well, and the call returns (index
     of the best candidate, x_raw (S, D), (S,) acquisition values); default
-    ramp only."""
+    ramp only.
+
+    With a ``DrawRequest`` that carries a ledger (only behind
+    ``fused_step_entry``) the advance half runs inside that call too, and the
+    call returns (index of the best candidate, x_raw (S, D)), or an
+    ``Advance`` when the native call did not draw: the suggest then goes on
+    with a ``DrawRequest`` of the rows found."""
     mirror = _mirror_of(cache)
+    if isinstance(fused, DrawRequest) and fused.ledger is not None:
+        return mirror.step_fused(
+            cache, fused, consider_endpoints, consider_magic_clip, prior_weight
+        )
     if isinstance(fused, DrawRequest):
         return mirror.draw_score_fused(
             cache, fused, consider_endpoints, consider_magic_clip, prior_weight

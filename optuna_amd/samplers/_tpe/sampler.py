@@ -488,7 +488,12 @@ class TPESampler(BaseSampler):
         # Native advance route (see _device.advance_fused_resident): with the
         # history's split ledger, one native call stands for the split, the
         # mirror sync, the exclusion list and the launch of the above-set fit.
+        # Native step route (see _device.fused_step_entry): where it is known
+        # here that the suggest ends on the native draw route, the two RNG
+        # calls of that route are made now (nothing before them draws) and
+        # the advance, the draw and the scoring are one native call.
         advance = None
+        early_draw: tuple[np.ndarray, np.ndarray] | None = None
         if (
             not per_dim
             and n_liar == 0
@@ -497,7 +502,38 @@ class TPESampler(BaseSampler):
             and p.prior_weight >= 0
         ):
             ledger = history.ledger_for(study)
-            if ledger is not None:
+            step_entry = None
+            if ledger is not None and self._n_ei_candidates > 0:
+                step_entry = _device.fused_step_entry(cache, n_below)
+            if step_entry is not None:
+                early_draw = self._draw_uniforms(len(cache.names))
+                out = _device.score_above_resident(
+                    cache,
+                    None,
+                    None,
+                    None,
+                    p.consider_endpoints,
+                    p.consider_magic_clip,
+                    prior_weight=p.prior_weight,
+                    fused=_device.DrawRequest(
+                        None,
+                        0,
+                        self._below_weights(
+                            min(n_below, cache._n_rows), study._is_multi_objective()
+                        ),
+                        *early_draw,
+                        step_entry,
+                        ledger,
+                        n_below,
+                    ),
+                )
+                if not isinstance(out, _device.Advance):
+                    return self._chosen_candidate(search_space, cache.names, *out)
+                # Not drawn: the below weights did not fit the below set. The
+                # fit runs; go on as behind the advance call, with these draws.
+                advance = out
+                assert advance.launched
+            elif ledger is not None:
                 advance = _device.advance_fused_resident(
                     cache,
                     ledger,
@@ -603,11 +639,9 @@ class TPESampler(BaseSampler):
             below_weights = self._below_weights(n_below_valid, study._is_multi_objective())
             if self._n_ei_candidates > 0 and _device.native_draw(cache):
                 # Native draw route: the two RNG calls of the draw, in its
-                # order, then one native call up to the chosen candidate.
-                u = self._rng.rng.random_sample(self._n_ei_candidates)
-                q = self._rng.rng.uniform(
-                    low=0, high=1, size=(self._n_ei_candidates, len(cache.names))
-                )
+                # order (made already on the way through the step route),
+                # then one native call up to the chosen candidate.
+                u, q = early_draw or self._draw_uniforms(len(cache.names))
                 best, x_below, _ = _device.score_above_resident(
                     cache,
                     None,
@@ -620,11 +654,8 @@ class TPESampler(BaseSampler):
                         below_rows, n_above, below_weights, u, q, below_native
                     ),
                 )
-                chosen = dict(zip(cache.names, x_below[best].tolist()))
-                return {
-                    name: dist.to_external_repr(chosen[name])
-                    for name, dist in search_space.items()
-                }
+                return self._chosen_candidate(search_space, cache.names, best, x_below)
+            assert early_draw is None  # every route from here on draws by itself
             x_below, below_mus, below_sigmas = _device.draw_below_native(
                 below_native,
                 cache,
@@ -637,6 +668,7 @@ class TPESampler(BaseSampler):
             )
             samples_below = {name: x_below[:, i] for i, name in enumerate(cache.names)}
         else:
+            assert early_draw is None
             obs_below, orders_below = history.observations(search_space, below_rows, cache)
             mpe_below = self._build_mpe(
                 study, search_space, obs_below, handle_below=True, orders=orders_below
@@ -739,6 +771,25 @@ class TPESampler(BaseSampler):
                 )
             return ret
         return self._best_candidate(search_space, samples_below, acq_func_vals)
+
+    def _draw_uniforms(self, n_dims: int) -> tuple[np.ndarray, np.ndarray]:
+        """The two RNG calls of the native draw route, in its order: (S,) for
+        the kernel choice, (S, D) for the quantile."""
+        u = self._rng.rng.random_sample(self._n_ei_candidates)
+        q = self._rng.rng.uniform(low=0, high=1, size=(self._n_ei_candidates, n_dims))
+        return u, q
+
+    @staticmethod
+    def _chosen_candidate(
+        search_space: dict[str, BaseDistribution],
+        names: Sequence[str],
+        best: int,
+        x_raw: np.ndarray,
+    ) -> dict[str, Any]:
+        chosen = dict(zip(names, x_raw[best].tolist()))
+        return {
+            name: dist.to_external_repr(chosen[name]) for name, dist in search_space.items()
+        }
 
     @staticmethod
     def _best_candidate(

@@ -10,7 +10,12 @@ work ahead of the fit is timed too: ``_TpeHistory.update``, ``_TpeHistory.split`
 the whole Python call ``_SpaceDeviceMirror.prepare_fused`` (which contains the
 native ``fused_prepare``) and, on a build with the native split ledger, the
 native ``fused_advance`` and the mirror's ``advance_fused`` around it;
-``host_before_fit_us`` is the median of ``update + split + (prepare_fused -
+on a build with the native step route, the one native ``fused_step`` that
+stands for ``fused_advance`` + ``fused_draw_score`` and the mirror's
+``step_fused`` around it (``OPTUNA_AMD_TPE_NATIVE_STEP=0`` times the old pair
+on such a build). ``between_calls`` is the Python stretch of the two-call
+route from the return of ``fused_advance`` to the entry of
+``fused_draw_score``, which the one call removes. ``host_before_fit_us`` is the median of ``update + split + (prepare_fused -
 fused_prepare)`` per step, where a step made all of those calls. Prints one
 JSON line with the median, the 10th/90th percentiles and min/max in
 microseconds, plus the suggest+tell rate of the timed steps.
@@ -41,6 +46,12 @@ class _TimedHistory:
     def __init__(self, hist, times: dict[str, list[float]]) -> None:
         self._hist = hist
         self._times = times
+        self._advance_end: float | None = None
+
+    def fused_step(self, *args):
+        # A method of the class: the sampler looks the step entry up on the
+        # history's type, and a build without it never calls this.
+        return self.__getattr__("fused_step")(*args)
 
     def __getattr__(self, name):
         attr = getattr(self._hist, name)
@@ -50,8 +61,14 @@ class _TimedHistory:
 
         def timed(*args, **kwargs):
             t0 = time.perf_counter()
+            if name == "fused_draw_score" and self._advance_end is not None:
+                self._times["between_calls"].append(t0 - self._advance_end)
+                self._advance_end = None
             out = attr(*args, **kwargs)
-            bucket.append(time.perf_counter() - t0)
+            t1 = time.perf_counter()
+            bucket.append(t1 - t0)
+            if name == "fused_advance":
+                self._advance_end = t1
             return out
 
         return timed
@@ -88,7 +105,8 @@ def main() -> None:
         "fused_score": [], "fused_prepare": [], "tpe_below_kernels": [], "sample_locked": [],
         "fused_draw_score": [], "draw_below_native": [], "ppf": [], "score_fused": [],
         "best_candidate": [], "update": [], "split": [], "prepare_fused": [],
-        "fused_advance": [], "advance_fused": [],
+        "fused_advance": [], "advance_fused": [], "between_calls": [],
+        "fused_step": [], "step_fused": [],
     }
 
     def timed(fn, bucket: list[float]):
@@ -117,6 +135,8 @@ def main() -> None:
     mirror_cls.prepare_fused = timed(mirror_cls.prepare_fused, times["prepare_fused"])
     if hasattr(mirror_cls, "advance_fused"):
         mirror_cls.advance_fused = timed(mirror_cls.advance_fused, times["advance_fused"])
+    if hasattr(mirror_cls, "step_fused"):
+        mirror_cls.step_fused = timed(mirror_cls.step_fused, times["step_fused"])
     from optuna_amd.samplers._tpe._history import _TpeHistory
 
     _TpeHistory.update = timed(_TpeHistory.update, times["update"])
@@ -174,7 +194,9 @@ def main() -> None:
     for _ in range(args.steps):
         one_step()
     wall = time.perf_counter() - t0
-    n_scored = len(times["fused_score"]) + len(times["fused_draw_score"])
+    n_scored = (
+        len(times["fused_score"]) + len(times["fused_draw_score"]) + len(times["fused_step"])
+    )
     assert n_scored == args.steps, "the fused path was not taken"
 
     host_before_fit = None
@@ -205,6 +227,9 @@ def main() -> None:
                 "prepare_fused": _stats(times["prepare_fused"]),
                 "fused_advance": _stats(times["fused_advance"]),
                 "advance_fused": _stats(times["advance_fused"]),
+                "between_calls": _stats(times["between_calls"]),
+                "fused_step": _stats(times["fused_step"]),
+                "step_fused": _stats(times["step_fused"]),
                 "host_before_fit_us": host_before_fit,
             }
         ),
