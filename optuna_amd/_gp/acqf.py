@@ -728,7 +728,7 @@ class LogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
         )
 
 
-class qLogEHVI(BaseAcquisitionFunc):
+class qLogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
     def __init__(
         self,
         gpr_list: list[GPRegressor],
@@ -756,6 +756,7 @@ class qLogEHVI(BaseAcquisitionFunc):
             lower, upper = _get_boxes(Y_fantasy, ref_point)
             lower_list.append(lower)
             interval_list.append((upper - lower).clamp_min_(_EPS))
+        self._box_counts = [len(lower) for lower in lower_list]
         self._box_lower = torch.nn.utils.rnn.pad_sequence(lower_list, batch_first=True).to(dev)
         self._box_intervals = torch.nn.utils.rnn.pad_sequence(
             interval_list, batch_first=True, padding_value=_EPS
@@ -778,6 +779,65 @@ class qLogEHVI(BaseAcquisitionFunc):
     def eval_acqf(self, x: "torch.Tensor") -> "torch.Tensor":
         log_utils = self.compute_per_sample_log_utility(x)
         return torch.special.logsumexp(log_utils, dim=-1) - math.log(log_utils.shape[-1])
+
+    # ---- fused K5 device path -------------------------------------------------------
+    # A parallel multi-objective study has running trials at every suggest, so
+    # this, not LogEHVI, is what it evaluates. The torch evaluation above builds
+    # a (B, n_qmc, n_boxes, M) tensor per call and its autograd copies. The
+    # session takes the base GPs as the LogEHVI session does, from every
+    # conditioned regressor what the qLogEI session takes, and the boxes of
+    # each draw packed one after another, without the padding rows. Taken for
+    # 2..4 objectives on device GPs of equal shape, up to 64 running trials and
+    # GP_QEHVI_MAX_Q draws; everything else keeps the torch path.
+    # OPTUNA_AMD_GP_FUSED_QEHVI=0 forces the torch path (A/B runs).
+
+    def _build_fused_session(self):
+        conds = self._cond_gpr_list
+        gprs = [cond._gpr for cond in conds]
+        shape = gprs[0]._X_train.shape
+        n_draws, n_running = conds[0]._fantasy_samples.shape
+        if (
+            self._device is None
+            or os.environ.get("OPTUNA_AMD_GP_FUSED_QEHVI", "1") == "0"
+            or not 2 <= len(gprs) <= 4
+            or any(not _device_ready(g) or g._X_train.shape != shape for g in gprs)
+            or n_running > _QLOGEI_MAX_R
+            or self._box_lower.shape[1] < 1
+        ):
+            return None
+        core = _fused_core()
+        if core is None or n_draws > core.GP_QEHVI_MAX_Q:
+            return None
+        # V_r is the transpose of a contiguous (R, N) tensor: column-major (N, R).
+        running = [
+            [conds[0]._X_running.contiguous()],
+            [cond._V_r.transpose(-2, -1).contiguous() for cond in conds],
+            [cond._cov_rr_post_chol.contiguous() for cond in conds],
+            [cond._cov_rr_post_inv_delta_r.contiguous() for cond in conds],
+        ]
+        # After the copies above: _device_tensors synchronises with torch's stream.
+        self._fused_refs = _device_tensors(gprs) + running
+        (Xr_ptr,), Vr_ptrs, L_ptrs, W_ptrs = _pointers(running)
+        counts = np.asarray(self._box_counts, dtype=np.int64)
+        real = np.arange(self._box_lower.shape[1]) < counts[:, None]  # (Q, Jmax)
+        return core.GpQLogEhviSession(
+            *_pointers(self._fused_refs[:4]),
+            [float(g.kernel_scale.item()) for g in gprs],
+            int(shape[0]),
+            int(shape[1]),
+            float(conds[0]._stabilizing_noise),
+            Xr_ptr,
+            Vr_ptrs,
+            L_ptrs,
+            W_ptrs,
+            int(n_running),
+            torch.stack([cond._fixed_samples_x for cond in conds], dim=-1).cpu().numpy(),
+            self._box_lower.cpu().numpy()[real],
+            self._box_intervals.cpu().numpy()[real],
+            np.concatenate([[0], np.cumsum(counts)]),
+            int(self._box_lower.shape[1]),
+            cat_mask=_cat_mask(gprs[0]._is_categorical),
+        )
 
 
 class LogCEHVI(_FusedEntryPoints, BaseAcquisitionFunc):

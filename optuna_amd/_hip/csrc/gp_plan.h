@@ -23,6 +23,15 @@ inline int64_t gp_chunk_rows(int64_t budget_bytes, int64_t N, int n_sets) {
     return std::clamp<int64_t>(budget_bytes / (3 * N * 8 * n_sets), 1, GP_GRID_Y_MAX);
 }
 
+// The same where a candidate also keeps `extra_doubles` doubles of scratch
+// outside the K / MP / V sets (per-draw buffers, which for small N outweigh
+// them). With none this is gp_chunk_rows.
+inline int64_t gp_chunk_rows_with(int64_t budget_bytes, int64_t N, int n_sets,
+                                  int64_t extra_doubles) {
+    return std::clamp<int64_t>(budget_bytes / ((3 * N * n_sets + extra_doubles) * 8), 1,
+                               GP_GRID_Y_MAX);
+}
+
 inline int64_t gp_n_chunks(int64_t B, int64_t rows) { return (B + rows - 1) / rows; }
 
 // Workgroups per candidate for a chunk of bc >= 1 candidates: towards

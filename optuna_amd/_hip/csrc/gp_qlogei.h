@@ -65,39 +65,23 @@ static size_t qlogei_lds_bytes(int R, int Q) {
            (((size_t)Q + 7) & ~size_t(7));
 }
 
-// One workgroup per candidate. All threads stage L and c; the first wavefront
-// does the two triangular solves with lane r owning row r (the R steps of
-// each are sequential, a step is parallel over the rows and the pivot travels
-// by a wavefront shuffle, so they need no block barrier); then all threads
-// walk the draws, q = tid, tid + 256, ..., reading 64 consecutive q of a row of
-// W per wavefront.
+// The conditioning of candidate b on the running rows, by a whole workgroup:
+// all threads stage L (pitch qlogei_ldl) and c = Kr - KVr in LDS and one adds
+// the candidate's S partial records; then the first wavefront does the two
+// triangular solves with lane r owning row r (the R steps of each are
+// sequential, a step is parallel over the rows and the pivot travels by a
+// wavefront shuffle, so they need no block barrier). On return, behind a
+// barrier: cs = c (R), post = K.alpha, K.V, quad and, with GRAD, ps = p (R).
 template <bool GRAD>
-__global__ void __launch_bounds__(GP_BLOCK)
-k_gp_qlogei_sample(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
-                   const double* __restrict__ Kr,    // (bc, R) = k(x, Xr)
-                   const double* __restrict__ KVr,   // (bc, R) = K @ Vr
-                   const double* __restrict__ L,     // (R, R) lower
-                   const double* __restrict__ W,     // (R, Q)
-                   const double* __restrict__ z,     // (Q)
-                   const double* __restrict__ m,     // (Q)
-                   double scale, double stab_noise, double threshold, int S,
-                   int R, int Q,
-                   double* __restrict__ out_f,    // (bc)
-                   double* __restrict__ out_wm,   // (bc), GRAD only
-                   double* __restrict__ out_wv,   // (bc), GRAD only
-                   double* __restrict__ out_u) {  // (bc, R), GRAD only
-    extern __shared__ double qlogei_lds[];
-    const int ldl = qlogei_ldl(R);
-    double* Ls = qlogei_lds;
-    double* cs = Ls + (size_t)R * ldl;
-    double* ps = cs + R;
-    double* sw = ps + R;
-    double* post = sw + R;  // K.alpha, K.V, quad
-    double* red = post + 3;
-    unsigned char* flag = reinterpret_cast<unsigned char*>(red + GP_WAVES);
-
+__device__ __forceinline__ void
+qlogei_condition(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
+                 const double* __restrict__ Kr,    // (bc, R) = k(x, Xr)
+                 const double* __restrict__ KVr,   // (bc, R) = K @ Vr
+                 const double* __restrict__ L,     // (R, R) lower
+                 int S, int R, int64_t b, double* Ls, double* cs, double* ps,
+                 double* post) {
     const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
+    const int ldl = qlogei_ldl(R);
     for (int i = tid; i < R * R; i += GP_BLOCK) Ls[(i / R) * ldl + (i % R)] = L[i];
     if (tid < R) cs[tid] = Kr[b * R + tid] - KVr[b * R + tid];
     if (tid == GP_BLOCK - 1) {
@@ -142,6 +126,39 @@ k_gp_qlogei_sample(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
         }
     }
     __syncthreads();
+}
+
+// One workgroup per candidate: qlogei_condition, then all threads walk the
+// draws, q = tid, tid + 256, ..., reading 64 consecutive q of a row of W per
+// wavefront.
+template <bool GRAD>
+__global__ void __launch_bounds__(GP_BLOCK)
+k_gp_qlogei_sample(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
+                   const double* __restrict__ Kr,    // (bc, R) = k(x, Xr)
+                   const double* __restrict__ KVr,   // (bc, R) = K @ Vr
+                   const double* __restrict__ L,     // (R, R) lower
+                   const double* __restrict__ W,     // (R, Q)
+                   const double* __restrict__ z,     // (Q)
+                   const double* __restrict__ m,     // (Q)
+                   double scale, double stab_noise, double threshold, int S,
+                   int R, int Q,
+                   double* __restrict__ out_f,    // (bc)
+                   double* __restrict__ out_wm,   // (bc), GRAD only
+                   double* __restrict__ out_wv,   // (bc), GRAD only
+                   double* __restrict__ out_u) {  // (bc, R), GRAD only
+    extern __shared__ double qlogei_lds[];
+    const int ldl = qlogei_ldl(R);
+    double* Ls = qlogei_lds;
+    double* cs = Ls + (size_t)R * ldl;
+    double* ps = cs + R;
+    double* sw = ps + R;
+    double* post = sw + R;  // K.alpha, K.V, quad
+    double* red = post + 3;
+    unsigned char* flag = reinterpret_cast<unsigned char*>(red + GP_WAVES);
+
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    qlogei_condition<GRAD>(part, Kr, KVr, L, S, R, b, Ls, cs, ps, post);
 
     const double kmean = post[0];
     const double raw = scale - post[1];

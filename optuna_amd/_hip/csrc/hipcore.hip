@@ -8,6 +8,7 @@
 #include "gp_logei.h"
 #include "gp_ehvi.h"
 #include "gp_qlogei.h"
+#include "gp_qlogehvi.h"
 
 #include "mo_host.h"
 #include "mo_rank.h"
@@ -82,6 +83,28 @@ PYBIND11_MODULE(_hipcore, m) {
     m.attr("GP_EHVI_BOX_TILE") = py::int_(EHVI_BOX_TILE);
     m.attr("GP_EHVI_MAX_Q") = py::int_(EHVI_MAX_Q);
     m.attr("GP_EHVI_SCRATCH_BUDGET_BYTES") = py::int_(GP_SCRATCH_BUDGET_BYTES);
+    py::class_<GpQLogEhviSession>(m, "GpQLogEhviSession")
+        .def(py::init<const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<double>&, int64_t, int64_t, double, int64_t,
+                      const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<int64_t>&, int64_t, const arr_f64&,
+                      const arr_f64&, const arr_f64&, const arr_i64&, int64_t,
+                      int64_t, uint64_t>(),
+             py::arg("X_ptrs"), py::arg("alpha_ptrs"), py::arg("cinv_ptrs"),
+             py::arg("eta_ptrs"), py::arg("scales"), py::arg("N"), py::arg("D"),
+             py::arg("stab_noise"), py::arg("Xr_ptr"), py::arg("Vr_ptrs"),
+             py::arg("L_ptrs"), py::arg("W_ptrs"), py::arg("R"), py::arg("z"),
+             py::arg("lo"), py::arg("iv"), py::arg("offsets"), py::arg("Jmax"),
+             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES,
+             py::arg("cat_mask") = (uint64_t)0)
+        .def("n_chunks", &GpQLogEhviSession::n_chunks, py::arg("B"),
+             py::arg("with_grad"))
+        .def("n_splits", &GpQLogEhviSession::n_splits, py::arg("bc"))
+        .def("draw_splits", &GpQLogEhviSession::draw_splits, py::arg("bc"))
+        .def("eval", &GpQLogEhviSession::eval, py::arg("x"), py::arg("with_grad"));
+    m.attr("GP_QEHVI_MAX_Q") = py::int_(QEHVI_MAX_Q);
+    m.attr("GP_QEHVI_TILE") = py::int_(QEHVI_TILE);
     py::class_<Hssp3dSession>(m, "Hssp3dSession")
         .def(py::init<const arr_f64&, double, double, double>(), py::arg("cand"),
              py::arg("ref_x"), py::arg("ref_y"), py::arg("ref_z"))
