@@ -16,7 +16,10 @@ import numpy as np
 
 from optuna_amd._gp.gp import ConditionalGPRegressor, GPRegressor
 from optuna_amd._gp.qmc import sample_from_normal_sobol
-from optuna_amd._hypervolume.box_decomposition import get_non_dominated_box_bounds
+from optuna_amd._hypervolume.box_decomposition import (
+    get_non_dominated_box_bounds,
+    get_non_dominated_boxes_batched,
+)
 from optuna_amd.study._multi_objective import _is_pareto_front
 
 
@@ -132,6 +135,23 @@ def _get_boxes(Y: "torch.Tensor", ref_point: np.ndarray) -> tuple["torch.Tensor"
     front = kept[_is_pareto_front(kept, assume_unique_lexsorted=False)]
     box_lo, box_hi = get_non_dominated_box_bounds(front, ref_point)
     return torch.from_numpy(-box_hi), torch.from_numpy(-box_lo)
+
+
+def _get_boxes_batched(
+    Y: "torch.Tensor", Y_extra: "torch.Tensor | None", ref_point: np.ndarray
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Packed max-space (lower, intervals, offsets) of the boxes of every draw.
+
+    Draw q is ``_get_boxes(cat(Y, Y_extra[q]))`` with the intervals clamped to
+    ``_EPS``; ``Y_extra`` (Q, R, M) may be None for the one draw of ``Y`` alone.
+    Large fronts of 2..4 objectives are decomposed on the device.
+    """
+    losses = np.asarray(-Y, dtype=np.float64)
+    if Y_extra is None:
+        extra = np.empty((1, 0, losses.shape[-1]))
+    else:
+        extra = np.asarray(-Y_extra, dtype=np.float64)
+    return get_non_dominated_boxes_batched(losses, extra, ref_point)
 
 
 def _fantasize(
@@ -672,9 +692,9 @@ class LogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
             dim=Y_train.shape[-1], n_samples=n_qmc_samples, seed=qmc_seed, device=dev
         )
         ref_point = _get_reference_point(Y_train)
-        box_lower, box_upper = _get_boxes(Y_train, ref_point)
-        self._box_lower = box_lower.to(dev)
-        self._box_intervals = (box_upper - box_lower).clamp_min_(_EPS).to(dev)
+        box_lower, box_intervals, _ = _get_boxes_batched(Y_train, None, ref_point)
+        self._box_lower = torch.from_numpy(box_lower).to(dev)
+        self._box_intervals = torch.from_numpy(box_intervals).to(dev)
         super().__init__(
             np.mean([gpr.length_scales for gpr in gpr_list], axis=0), search_space, dev
         )
@@ -748,19 +768,22 @@ class qLogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
         ]
         dev = gpr_list[0].device
         ref_point = _get_reference_point(Y_train)
-        lower_list, interval_list = [], []
-        for fantasy in torch.stack(
+        fantasies = torch.stack(
             [cg.get_fantasy_samples().cpu() for cg in self._cond_gpr_list], dim=-1
-        ):
-            Y_fantasy = torch.cat([Y_train, fantasy], dim=0)
-            lower, upper = _get_boxes(Y_fantasy, ref_point)
-            lower_list.append(lower)
-            interval_list.append((upper - lower).clamp_min_(_EPS))
-        self._box_counts = [len(lower) for lower in lower_list]
-        self._box_lower = torch.nn.utils.rnn.pad_sequence(lower_list, batch_first=True).to(dev)
-        self._box_intervals = torch.nn.utils.rnn.pad_sequence(
-            interval_list, batch_first=True, padding_value=_EPS
-        ).to(dev)
+        )  # (Q, R, M)
+        # Every draw's boxes in one call, packed draw after draw; the torch
+        # evaluation takes them padded to the longest draw (0 and _EPS).
+        lower, intervals, offsets = _get_boxes_batched(Y_train, fantasies, ref_point)
+        self._box_packed = (lower, intervals, offsets)
+        counts = np.diff(offsets)
+        self._box_counts = [int(c) for c in counts]
+        real = np.arange(int(counts.max())) < counts[:, None]  # (Q, Jmax)
+        lower_padded = np.zeros(real.shape + lower.shape[-1:])
+        intervals_padded = np.full(real.shape + lower.shape[-1:], _EPS)
+        lower_padded[real] = lower
+        intervals_padded[real] = intervals
+        self._box_lower = torch.from_numpy(lower_padded).to(dev)
+        self._box_intervals = torch.from_numpy(intervals_padded).to(dev)
         super().__init__(
             np.mean([gpr.length_scales for gpr in gpr_list], axis=0), search_space, dev
         )
@@ -818,8 +841,7 @@ class qLogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
         # After the copies above: _device_tensors synchronises with torch's stream.
         self._fused_refs = _device_tensors(gprs) + running
         (Xr_ptr,), Vr_ptrs, L_ptrs, W_ptrs = _pointers(running)
-        counts = np.asarray(self._box_counts, dtype=np.int64)
-        real = np.arange(self._box_lower.shape[1]) < counts[:, None]  # (Q, Jmax)
+        lower, intervals, offsets = self._box_packed
         return core.GpQLogEhviSession(
             *_pointers(self._fused_refs[:4]),
             [float(g.kernel_scale.item()) for g in gprs],
@@ -832,9 +854,9 @@ class qLogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):
             W_ptrs,
             int(n_running),
             torch.stack([cond._fixed_samples_x for cond in conds], dim=-1).cpu().numpy(),
-            self._box_lower.cpu().numpy()[real],
-            self._box_intervals.cpu().numpy()[real],
-            np.concatenate([[0], np.cumsum(counts)]),
+            lower,
+            intervals,
+            offsets,
             int(self._box_lower.shape[1]),
             cat_mask=_cat_mask(gprs[0]._is_categorical),
         )

@@ -10,6 +10,7 @@
 #include "gp_qlogei.h"
 #include "gp_qlogehvi.h"
 
+#include "mo_boxes.h"
 #include "mo_host.h"
 #include "mo_rank.h"
 #include "tpe_host.h"
@@ -126,6 +127,10 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("ref_y"), py::arg("ref_z"))
         .def("run", &Hssp4dSession::run, py::arg("subset_size"));
     m.attr("HSSP4D_MAX_SUBSET") = py::int_(HSSP4_MAX_K);
+    m.def("box_decompose", &box_decompose, py::arg("base"), py::arg("extra"),
+          py::arg("ref"), py::kw_only(), py::arg("active_cap") = 0,
+          py::arg("out_cap") = 0);
+    m.def("box_decompose_limits", &box_decompose_limits, py::arg("n_objectives"));
     m.def("kde_logpdf", &kde_logpdf, py::arg("obs"), py::arg("sorted_pos"),
           py::arg("logw"), py::arg("alow"), py::arg("ahigh"), py::arg("steps"),
           py::arg("n_choices"), py::arg("prior_weight"),

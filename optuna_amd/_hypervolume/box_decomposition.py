@@ -12,6 +12,7 @@ _get_upper_bound_set :30, _get_box_bounds :96, get_non_dominated_box_bounds
 """
 from __future__ import annotations
 
+import os
 import warnings
 
 import numpy as np
@@ -128,3 +129,94 @@ def get_non_dominated_box_bounds(
     )
     box_upper, box_lower = -_get_box_bounds(neg_lower_set, neg_dps, inf_point)
     return box_lower, box_upper
+
+
+_INTERVAL_EPS = 1e-12  # the acquisition's clamp: a zero interval has a NaN gradient
+
+# Fewest rows (base rows below the reference point plus a draw's own rows) per
+# number of objectives from which the device decomposes: the smallest sizes of
+# scripts/box_decomposition_timing.py (docs/PERF.md, "Box decomposition on the
+# device"), 16 + 8 rows for two objectives and 4 + 8 for three and four. The
+# device won there by 4.8x, 4.3x and 6.8x with one draw, and by more at every
+# larger size and with 128 draws; nothing smaller was measured.
+_DEVICE_BOXES_MIN_ROWS = {2: 24, 3: 12, 4: 12}
+
+
+def _boxes_host(
+    base_losses: np.ndarray, extra_rows: np.ndarray, ref_point: np.ndarray
+) -> tuple[np.ndarray, np.ndarray]:
+    """Max-space (lower, intervals) of one draw: the acquisition's ``_get_boxes``."""
+    losses = np.concatenate([base_losses, extra_rows], axis=0)
+    kept = losses[(losses < ref_point).all(axis=-1)]
+    front = kept[_is_pareto_front(kept, assume_unique_lexsorted=False)]
+    box_lo, box_hi = get_non_dominated_box_bounds(front, ref_point)
+    # Negating swaps the roles of the bounds.
+    lower, upper = -box_hi, -box_lo
+    return lower, np.maximum(upper - lower, _INTERVAL_EPS)
+
+
+def _boxes_device(
+    base_losses: np.ndarray, extra_losses: np.ndarray, ref_point: np.ndarray
+) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray] | None:
+    """K6e HIP path: every draw's boxes in one launch train (or None)."""
+    n_objectives = ref_point.shape[0]
+    n_rows = base_losses.shape[0] + extra_losses.shape[1]
+    if (
+        os.environ.get("OPTUNA_AMD_GP_BOXES_DEVICE", "1") == "0"
+        or n_objectives not in _DEVICE_BOXES_MIN_ROWS
+        or n_rows < _DEVICE_BOXES_MIN_ROWS[n_objectives]
+        or not (np.isfinite(base_losses).all() and np.isfinite(extra_losses).all())
+        or not np.isfinite(ref_point).all()
+    ):
+        return None
+    from optuna_amd import _hip
+
+    core = _hip.get()
+    if core is None or not core.available():
+        return None
+    return core.box_decompose(base_losses, extra_losses, ref_point)
+
+
+def get_non_dominated_boxes_batched(
+    base_losses: np.ndarray, extra_losses: np.ndarray, ref_point: np.ndarray
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Boxes of the non-dominated region of ``base | extra[q]`` for every draw q.
+
+    base_losses: (n0, k) rows shared by the draws; extra_losses: (Q, R, k), the
+    rows of each draw (R may be 0); all in loss (minimization) space. Returns
+    packed max-space ``(lower, intervals, offsets)``: the boxes of draw q are
+    rows ``offsets[q]:offsets[q + 1]``, the same set as the acquisition's
+    per-draw decomposition of ``concatenate([base, extra[q]])`` with the
+    intervals clamped to 1e-12. The order of a draw's boxes depends on the
+    route (host or device) and is the same from run to run.
+    """
+    base_losses = np.ascontiguousarray(base_losses, dtype=np.float64)
+    extra_losses = np.ascontiguousarray(extra_losses, dtype=np.float64)
+    ref_point = np.ascontiguousarray(ref_point, dtype=np.float64)
+    n_draws, _, k = extra_losses.shape
+    assert base_losses.ndim == 2 and base_losses.shape[1] == k == ref_point.shape[0]
+
+    kept = base_losses[(base_losses < ref_point).all(axis=-1)]
+    # The device reduces the rows to their front itself, per draw.
+    device = _boxes_device(kept, extra_losses, ref_point)
+    if device is not None and len(device[3]) == 0:
+        return device[:3]
+    # The front of base | extra[q] is the front of front(base) | extra[q]: the
+    # host reduces the base once for all draws.
+    base_front = kept[_is_pareto_front(kept, assume_unique_lexsorted=False)]
+    if device is None:
+        per_draw = [_boxes_host(base_front, extra_losses[q], ref_point) for q in range(n_draws)]
+    else:
+        lower, intervals, offsets, host_needed = device
+        per_draw = [
+            (lower[offsets[q] : offsets[q + 1]], intervals[offsets[q] : offsets[q + 1]])
+            for q in range(n_draws)
+        ]
+        for q in host_needed:
+            per_draw[q] = _boxes_host(base_front, extra_losses[q], ref_point)
+    offsets = np.concatenate([[0], np.cumsum([len(lo) for lo, _ in per_draw])]).astype(np.int64)
+    return (
+        np.concatenate([lo for lo, _ in per_draw], axis=0).reshape(-1, k),
+        np.concatenate([iv for _, iv in per_draw], axis=0).reshape(-1, k),
+        offsets,
+    )
