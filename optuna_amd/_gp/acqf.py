@@ -404,7 +404,7 @@ class qLogEI(_FusedEntryPoints, BaseAcquisitionFunc):
     # deviations and the QMC normals of the candidate column. The fantasies
     # themselves enter only through their best improvement per draw. Taken for
     # up to 64 running trials and 1024 draws; anything else keeps the torch
-    # path above, as qLogCEI always does.
+    # path above.
 
     def _build_fused_session(self):
         cond = self._cond_gpr
@@ -624,7 +624,7 @@ class LogCEI(_FusedEntryPoints, BaseAcquisitionFunc):
         )
 
 
-class qLogCEI(BaseAcquisitionFunc):
+class qLogCEI(_FusedEntryPoints, BaseAcquisitionFunc):
     def __init__(
         self,
         gpr: GPRegressor,
@@ -665,6 +665,75 @@ class qLogCEI(BaseAcquisitionFunc):
             acqf.compute_per_sample_log_utility(x) for acqf in self._constraints_acqf_list
         )
         return _mean_max_log_utility(log_feasible_improvement)
+
+    # ---- fused K5 device path -------------------------------------------------------
+    # A constrained single-objective study with two or more workers evaluates
+    # this at every suggest. The session takes the 1 + C conditioned regressors
+    # as the qLogEHVI session takes its objectives (with a threshold of -inf,
+    # no feasible trial yet, the C constraints alone) and runs every per-GP
+    # stage as one launch over all of them. The fantasy columns do not move with
+    # the candidate: they enter as F_q, their best utility per draw, computed
+    # here once. Taken for device GPs of equal shape, up to GP_FEAS_MAX_C
+    # constraints, 64 running trials and 1024 draws; everything else keeps the
+    # torch path above. OPTUNA_AMD_GP_FUSED_CONSTRAINED=0 forces it (A/B runs).
+
+    def _build_fused_session(self):
+        has_objective = not np.isneginf(self._acqf._threshold)
+        members = ([self._acqf] if has_objective else []) + self._constraints_acqf_list
+        conds = [a._cond_gpr for a in members]
+        gprs = [cond._gpr for cond in conds]
+        shape = gprs[0]._X_train.shape
+        n_draws, n_running = conds[0]._fantasy_samples.shape
+        if (
+            self._device is None
+            or os.environ.get("OPTUNA_AMD_GP_FUSED_CONSTRAINED", "1") == "0"
+            or any(not _device_ready(g) or g._X_train.shape != shape for g in gprs)
+            or n_running > _QLOGEI_MAX_R
+            or n_draws > _QLOGEI_MAX_Q
+        ):
+            return None
+        core = _fused_core()
+        if core is None or len(self._constraints_acqf_list) > core.GP_FEAS_MAX_C:
+            return None
+        tau = self._constraints_acqf_list[0]._tau
+        fantasy_utility = sum(
+            torch.nn.functional.logsigmoid((a._cond_gpr._fantasy_samples - a._threshold) / a._tau)
+            for a in self._constraints_acqf_list
+        )
+        if has_objective:
+            fantasy_utility = fantasy_utility + (
+                (conds[0]._fantasy_samples - self._acqf._threshold).clamp_min(_EPS).log()
+            )
+        # V_r is the transpose of a contiguous (R, N) tensor: column-major (N, R).
+        running = [
+            [conds[0]._X_running.contiguous()],
+            [cond._V_r.transpose(-2, -1).contiguous() for cond in conds],
+            [cond._cov_rr_post_chol.contiguous() for cond in conds],
+            [cond._cov_rr_post_inv_delta_r.contiguous() for cond in conds],
+        ]
+        z = torch.stack([cond._fixed_samples_x for cond in conds], dim=-1).cpu().numpy()
+        best_fantasy = fantasy_utility.amax(dim=-1).cpu().numpy()
+        # After the copies above: _device_tensors synchronises with torch's stream.
+        self._fused_refs = _device_tensors(gprs) + running
+        (Xr_ptr,), Vr_ptrs, L_ptrs, W_ptrs = _pointers(running)
+        return core.GpQLogCeiSession(
+            *_pointers(self._fused_refs[:4]),
+            [float(g.kernel_scale.item()) for g in gprs],
+            int(shape[0]),
+            int(shape[1]),
+            float(conds[0]._stabilizing_noise),
+            Xr_ptr,
+            Vr_ptrs,
+            L_ptrs,
+            W_ptrs,
+            int(n_running),
+            [float(a._threshold) for a in members],
+            has_objective,
+            z,
+            best_fantasy,
+            float(tau),
+            cat_mask=_cat_mask(gprs[0]._is_categorical),
+        )
 
 
 class LogEHVI(_FusedEntryPoints, BaseAcquisitionFunc):

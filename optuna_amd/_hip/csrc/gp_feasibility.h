@@ -65,16 +65,18 @@ static int feas_words(int D, bool grad) { return grad ? 2 + 2 * D : 2; }
 // d over the rows g, g + G, ... of the slice (G = 256 / D groups), so X is read
 // along its rows and nothing is indexed at run time in registers; the d == 0
 // thread of a group also carries the two posterior sums of its rows.
+// The body is a device function so that the GP-batched launch of
+// gp_qlogcei.h runs the same code.
 template <bool GRAD>
-__global__ void __launch_bounds__(GP_BLOCK)
-k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
-                   const double* __restrict__ MP,     // (bc, N)
-                   const double* __restrict__ V,      // (bc, N) = K @ Cinv
-                   const double* __restrict__ alpha,  // (N)
-                   const double* __restrict__ X,      // (N, D)
-                   const double* __restrict__ x,      // (bc, D)
-                   int64_t N, int D, uint64_t cat_mask,
-                   double* __restrict__ part) {  // (bc, S, W)
+__device__ __forceinline__ void
+gp_logpi_partial_body(const double* __restrict__ K,      // (bc, N)
+                      const double* __restrict__ MP,     // (bc, N)
+                      const double* __restrict__ V,      // (bc, N) = K @ Cinv
+                      const double* __restrict__ alpha,  // (N)
+                      const double* __restrict__ X,      // (N, D)
+                      const double* __restrict__ x,      // (bc, D)
+                      int64_t N, int D, uint64_t cat_mask,
+                      double* __restrict__ part) {  // (bc, S, W)
     __shared__ double red[GP_WAVES];
     __shared__ double part_a[GRAD ? GP_BLOCK : 1];
     __shared__ double part_b[GRAD ? GP_BLOCK : 1];
@@ -140,6 +142,19 @@ k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
             rec[2 + D + tid] = bv;
         }
     }
+}
+
+template <bool GRAD>
+__global__ void __launch_bounds__(GP_BLOCK)
+k_gp_logpi_partial(const double* __restrict__ K,      // (bc, N)
+                   const double* __restrict__ MP,     // (bc, N)
+                   const double* __restrict__ V,      // (bc, N) = K @ Cinv
+                   const double* __restrict__ alpha,  // (N)
+                   const double* __restrict__ X,      // (N, D)
+                   const double* __restrict__ x,      // (bc, D)
+                   int64_t N, int D, uint64_t cat_mask,
+                   double* __restrict__ part) {  // (bc, S, W)
+    gp_logpi_partial_body<GRAD>(K, MP, V, alpha, X, x, N, D, cat_mask, part);
 }
 
 // One thread per candidate (per (candidate, d) with GRAD): the S partial

@@ -49,14 +49,18 @@ __device__ __forceinline__ double gp_block_sum(double v, double* red) {
 // the categorical columns of `cat_mask` (bit d = column d): there the term of
 // r2 is eta_d * [x_d != X_id], the Hamming indicator, in place of the squared
 // difference. MP stays the derivative with respect to r2 either way.
+// The body is a device function so that the GP-batched launch of
+// gp_qlogcei.h runs the same code; blockIdx.x walks the rows of X, blockIdx.y
+// is the candidate.
 template <bool MIXED>
-__global__ void k_gp_cross_cov(const double* __restrict__ X,  // (N, D)
-                               const double* __restrict__ eta,  // (D)
-                               double scale, const double* __restrict__ x,  // (B, D)
-                               int64_t N, int64_t D, int64_t B,
-                               double* __restrict__ K,    // (B, N)
-                               double* __restrict__ MP,   // (B, N) scale*m52'(r2)
-                               uint64_t cat_mask) {
+__device__ __forceinline__ void
+gp_cross_cov_body(const double* __restrict__ X,  // (N, D)
+                  const double* __restrict__ eta,  // (D)
+                  double scale, const double* __restrict__ x,  // (B, D)
+                  int64_t N, int64_t D,
+                  double* __restrict__ K,    // (B, N)
+                  double* __restrict__ MP,   // (B, N) scale*m52'(r2)
+                  uint64_t cat_mask) {
     __shared__ double xs[64];
     __shared__ double et[64];
     const int64_t b = blockIdx.y;
@@ -82,6 +86,17 @@ __global__ void k_gp_cross_cov(const double* __restrict__ X,  // (N, D)
     const double eu = exp(-u);
     K[b * N + i] = scale * (eu * ((5.0 / 3.0) * r2 + u + 1.0));
     MP[b * N + i] = scale * ((-5.0 / 6.0) * (1.0 + u) * eu);
+}
+
+template <bool MIXED>
+__global__ void k_gp_cross_cov(const double* __restrict__ X,  // (N, D)
+                               const double* __restrict__ eta,  // (D)
+                               double scale, const double* __restrict__ x,  // (B, D)
+                               int64_t N, int64_t D, int64_t B,
+                               double* __restrict__ K,    // (B, N)
+                               double* __restrict__ MP,   // (B, N) scale*m52'(r2)
+                               uint64_t cat_mask) {
+    gp_cross_cov_body<MIXED>(X, eta, scale, x, N, D, K, MP, cat_mask);
 }
 
 // One fitted GP on the device: X (N, D), alpha = Cinv @ y (N), the explicit

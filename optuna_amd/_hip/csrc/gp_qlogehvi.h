@@ -67,9 +67,11 @@ static size_t qehvi_cond_lds_doubles(int R) {
 // then all threads write s[b, q, m] for q = tid, tid + 256, ..., reading 64
 // consecutive q of a row of W per wavefront. With GRAD also p (R) and
 // post = sd, [cv_raw > 0], [raw >= 0] of the candidate.
+// The body is a device function so that the GP-batched launch of
+// gp_qlogcei.h runs the same code.
 template <bool GRAD>
-__global__ void __launch_bounds__(GP_BLOCK)
-k_gp_qehvi_cond(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
+__device__ __forceinline__ void
+qehvi_cond_body(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
                 const double* __restrict__ Kr,    // (bc, R) = k(x, Xr)
                 const double* __restrict__ KVr,   // (bc, R) = K @ Vr
                 const double* __restrict__ L,     // (R, R) lower
@@ -106,6 +108,22 @@ k_gp_qehvi_cond(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
             out_post[b * 3 + 2] = raw >= 0.0 ? 1.0 : 0.0;  // clamp_min passes it here
         }
     }
+}
+
+template <bool GRAD>
+__global__ void __launch_bounds__(GP_BLOCK)
+k_gp_qehvi_cond(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
+                const double* __restrict__ Kr,    // (bc, R) = k(x, Xr)
+                const double* __restrict__ KVr,   // (bc, R) = K @ Vr
+                const double* __restrict__ L,     // (R, R) lower
+                const double* __restrict__ W,     // (R, Q)
+                const double* __restrict__ z,     // (Q, M)
+                double scale, double stab_noise, int S, int R, int Q, int m, int M,
+                double* __restrict__ out_s,       // (bc, Q, M)
+                double* __restrict__ out_p,       // (bc, R), GRAD only
+                double* __restrict__ out_post) {  // (bc, 3), GRAD only
+    qehvi_cond_body<GRAD>(part, Kr, KVr, L, W, z, scale, stab_noise, S, R, Q, m, M,
+                          out_s, out_p, out_post);
 }
 
 // Words of one (candidate, draw) record: P_q, and with the gradient

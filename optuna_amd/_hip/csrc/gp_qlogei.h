@@ -211,8 +211,10 @@ k_gp_qlogei_sample(const double* __restrict__ part,  // (bc, S, 2): K.alpha, K.V
 // s == 0 of the R running rows after them, with thread (g, d) = (tid / D,
 // tid % D) as in k_gp_ehvi_grad. One record of D words,
 // x_d sum coef - sum coef X_.d, the G groups of a dimension added in order.
-__global__ void __launch_bounds__(GP_BLOCK)
-k_gp_qlogei_grad(const double* __restrict__ UV,     // (bc, N) = u @ Vr^T
+// The body is a device function so that the GP-batched launch of
+// gp_qlogcei.h runs the same code.
+__device__ __forceinline__ void
+qlogei_grad_body(const double* __restrict__ UV,     // (bc, N) = u @ Vr^T
                  const double* __restrict__ MP,     // (bc, N)
                  const double* __restrict__ V,      // (bc, N)
                  const double* __restrict__ alpha,  // (N)
@@ -264,6 +266,24 @@ k_gp_qlogei_grad(const double* __restrict__ UV,     // (bc, N) = u @ Vr^T
         for (int k = 1; k < G; ++k) out += part_s[k * D + tid];
         part[(b * S + blockIdx.y) * D + tid] = out;
     }
+}
+
+__global__ void __launch_bounds__(GP_BLOCK)
+k_gp_qlogei_grad(const double* __restrict__ UV,     // (bc, N) = u @ Vr^T
+                 const double* __restrict__ MP,     // (bc, N)
+                 const double* __restrict__ V,      // (bc, N)
+                 const double* __restrict__ alpha,  // (N)
+                 const double* __restrict__ X,      // (N, D)
+                 const double* __restrict__ x,      // (bc, D)
+                 const double* __restrict__ wm,     // (bc)
+                 const double* __restrict__ wv,     // (bc)
+                 const double* __restrict__ u,      // (bc, R)
+                 const double* __restrict__ MPr,    // (bc, R)
+                 const double* __restrict__ Xr,     // (R, D)
+                 int64_t N, int D, int R, uint64_t cat_mask,
+                 double* __restrict__ part) {  // (bc, S, D)
+    qlogei_grad_body(UV, MP, V, alpha, X, x, wm, wv, u, MPr, Xr, N, D, R, cat_mask,
+                     part);
 }
 
 // One thread per (candidate, d): the S records in order, times 2 eta_d;

@@ -9,6 +9,7 @@
 #include "gp_ehvi.h"
 #include "gp_qlogei.h"
 #include "gp_qlogehvi.h"
+#include "gp_qlogcei.h"
 
 #include "mo_boxes.h"
 #include "mo_host.h"
@@ -106,6 +107,26 @@ PYBIND11_MODULE(_hipcore, m) {
         .def("eval", &GpQLogEhviSession::eval, py::arg("x"), py::arg("with_grad"));
     m.attr("GP_QEHVI_MAX_Q") = py::int_(QEHVI_MAX_Q);
     m.attr("GP_QEHVI_TILE") = py::int_(QEHVI_TILE);
+    py::class_<GpQLogCeiSession>(m, "GpQLogCeiSession")
+        .def(py::init<const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<double>&, int64_t, int64_t, double, int64_t,
+                      const std::vector<int64_t>&, const std::vector<int64_t>&,
+                      const std::vector<int64_t>&, int64_t,
+                      const std::vector<double>&, bool, const arr_f64&,
+                      const arr_f64&, double, int64_t, uint64_t>(),
+             py::arg("X_ptrs"), py::arg("alpha_ptrs"), py::arg("cinv_ptrs"),
+             py::arg("eta_ptrs"), py::arg("scales"), py::arg("N"), py::arg("D"),
+             py::arg("stab_noise"), py::arg("Xr_ptr"), py::arg("Vr_ptrs"),
+             py::arg("L_ptrs"), py::arg("W_ptrs"), py::arg("R"),
+             py::arg("thresholds"), py::arg("has_objective"), py::arg("z"),
+             py::arg("F"), py::arg("tau"),
+             py::arg("scratch_budget_bytes") = GP_SCRATCH_BUDGET_BYTES,
+             py::arg("cat_mask") = (uint64_t)0)
+        .def("n_chunks", &GpQLogCeiSession::n_chunks, py::arg("B"),
+             py::arg("with_grad"))
+        .def("n_splits", &GpQLogCeiSession::n_splits, py::arg("bc"))
+        .def("eval", &GpQLogCeiSession::eval, py::arg("x"), py::arg("with_grad"));
     py::class_<Hssp3dSession>(m, "Hssp3dSession")
         .def(py::init<const arr_f64&, double, double, double>(), py::arg("cand"),
              py::arg("ref_x"), py::arg("ref_y"), py::arg("ref_z"))
