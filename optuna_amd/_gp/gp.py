@@ -13,6 +13,7 @@ path; set ``device`` to a CUDA/HIP device to move the linear algebra there.
 from __future__ import annotations
 
 import math
+import os
 from typing import TYPE_CHECKING, Any, Callable
 
 import numpy as np
@@ -575,6 +576,76 @@ class GPRegressor:
             )
             return float(loss.item()), grad.cpu().numpy()
 
+    # The fused evaluator's own floor, the stock device-fit threshold: it was
+    # timed from 512 observations up, and a device fit forced onto a smaller
+    # history (a lowered _DEVICE_FIT_MIN_OBS) keeps the torch chain's numbers.
+    _FUSED_FIT_MIN_OBS = 512
+
+    def _fused_fit_evaluator(
+        self,
+        X: "torch.Tensor",
+        y: "torch.Tensor",
+        minimum_noise: float,
+        deterministic_objective: bool,
+    ) -> "Callable[[np.ndarray], tuple[float, np.ndarray]] | None":
+        """The loss-and-gradient evaluator over a native ``GpFitSession``, or None.
+
+        What ``_loss_and_grad_closed_form_torch`` computes, with its elementwise
+        and reduction chains in two HIP kernels around torch's factorisation:
+        ``build_cov`` writes C in difference form, torch factors, solves and
+        inverts it exactly as there, ``grad`` reads Cinv once and returns the
+        loss and the gradient. Taken on a device fit of at least
+        ``_FUSED_FIT_MIN_OBS`` observations with the extension loaded and
+        D <= 64; OPTUNA_AMD_GP_FUSED_FIT=0 keeps the torch chain (A/B runs).
+        """
+        n_obs, n_params = X.shape
+        if (
+            not X.is_cuda
+            or n_obs < self._FUSED_FIT_MIN_OBS
+            or n_params > 64
+            or os.environ.get("OPTUNA_AMD_GP_FUSED_FIT", "1") == "0"
+        ):
+            return None
+        from optuna_amd import _hip
+
+        core = _hip.get()
+        if core is None or not core.available():
+            return None
+        # The session reads these through raw pointers: `evaluate` owns them
+        # (`contiguous()` of a strided X or y is a copy nobody else holds).
+        X_dev = X.contiguous()
+        y_dev = y.contiguous()
+        cat_mask = sum(1 << int(d) for d in np.flatnonzero(self._cat_host()))
+        # Our stream must not race torch's producers of X and y.
+        torch.cuda.synchronize()
+        session = core.GpFitSession(
+            X_dev.data_ptr(), y_dev.data_ptr(), int(n_obs), int(n_params), cat_mask=cat_mask
+        )
+        C = torch.empty((n_obs, n_obs), dtype=torch.float64, device=X.device)
+
+        def evaluate(
+            raw_params: np.ndarray, _keep: tuple = (X_dev, y_dev)
+        ) -> tuple[float, np.ndarray]:
+            raw = np.ascontiguousarray(raw_params, dtype=np.float64)
+            session.build_cov(raw, minimum_noise, deterministic_objective, C.data_ptr())
+            with torch.no_grad():
+                L = torch.linalg.cholesky(C)
+                alpha = torch.cholesky_solve(y_dev.unsqueeze(-1), L)[:, 0].contiguous()
+                Cinv = torch.cholesky_inverse(L)
+            # grad reads L, alpha and Cinv on the session's own stream.
+            torch.cuda.current_stream().synchronize()
+            loss, grad = session.grad(
+                raw,
+                minimum_noise,
+                deterministic_objective,
+                L.data_ptr(),
+                alpha.data_ptr(),
+                Cinv.data_ptr(),
+            )
+            return float(loss), grad
+
+        return evaluate
+
     # Move the fit to the GPU above this many observations: below it, kernel
     # launch latency beats the CPU BLAS; above, the O(N³) factorizations win.
     _DEVICE_FIT_MIN_OBS = 512
@@ -615,7 +686,15 @@ class GPRegressor:
             X = self._X_train
             y = self._y_train.squeeze(-1)
 
+            fused = (
+                self._fused_fit_evaluator(X, y, minimum_noise, deterministic_objective)
+                if use_device
+                else None
+            )
+
             def loss_func_closed(raw_params: np.ndarray) -> tuple[float, np.ndarray]:
+                if fused is not None:
+                    return fused(raw_params)
                 return self._loss_and_grad_closed_form_torch(
                     raw_params, X, y, minimum_noise, deterministic_objective
                 )

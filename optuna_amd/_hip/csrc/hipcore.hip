@@ -10,6 +10,7 @@
 #include "gp_qlogei.h"
 #include "gp_qlogehvi.h"
 #include "gp_qlogcei.h"
+#include "gp_fit.h"
 
 #include "mo_boxes.h"
 #include "mo_host.h"
@@ -127,6 +128,15 @@ PYBIND11_MODULE(_hipcore, m) {
              py::arg("with_grad"))
         .def("n_splits", &GpQLogCeiSession::n_splits, py::arg("bc"))
         .def("eval", &GpQLogCeiSession::eval, py::arg("x"), py::arg("with_grad"));
+    py::class_<GpFitSession>(m, "GpFitSession")
+        .def(py::init<int64_t, int64_t, int64_t, int64_t, uint64_t>(), py::arg("X_ptr"),
+             py::arg("y_ptr"), py::arg("N"), py::arg("D"), py::kw_only(),
+             py::arg("cat_mask") = (uint64_t)0)
+        .def("build_cov", &GpFitSession::build_cov, py::arg("raw_params"),
+             py::arg("minimum_noise"), py::arg("deterministic"), py::arg("C_ptr"))
+        .def("grad", &GpFitSession::grad, py::arg("raw_params"),
+             py::arg("minimum_noise"), py::arg("deterministic"), py::arg("L_ptr"),
+             py::arg("alpha_ptr"), py::arg("Cinv_ptr"));
     py::class_<Hssp3dSession>(m, "Hssp3dSession")
         .def(py::init<const arr_f64&, double, double, double>(), py::arg("cand"),
              py::arg("ref_x"), py::arg("ref_y"), py::arg("ref_z"))
